@@ -16,17 +16,28 @@ silently smaller benchmark.  Independent vectors per rank, no data-path collecti
 by vector) -> weak scaling; only the timing barrier and the rank count use RCCL.
 
 `--mode c5` is BASELINE config C5: 64 vectors of 1 048 576 points per GPU (512 on 8 GPUs), batched
-convolve_signal -> plain_fft.  `value` is the compute-only rate with the shards resident; the same
-line carries the end-to-end scatter + compute + gather time from rank 0 (chunked, pipelined:
+convolve_signal -> plain_fft.  `value` is the compute-only rate with the shards resident; with --full the
+same line carries the end-to-end scatter + compute + gather time from rank 0 (chunked, pipelined:
 basic_dsp_amd/batch.py) under `c5_end_to_end`.
 
-Whenever the ranks form a process group (N > 1, or --init-dist) the DEFAULT mode also runs and VERIFIES the path's one
-multi-GPU exchange after the timed region: a C5-shaped batch goes out from rank 0 in chunks over grouped point-to-point
-sends, every rank convolves + transforms, the spectra come back, and rank 0 compares the first and last chunk of every
-peer bit for bit with its own computation (`c5_end_to_end`: ms, Msamples_s, verified_rows, peers; a mismatch exits 3; a
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, the outputs of the last timed step
+when --dump-outputs DIR is given, and the JSON line with the contract's fields (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, ...).  Everything else the benchmark measures or checks -- the cold figure, the
+per-kernel event timings and `roofline` / `kernels`, `value_windows`, `self_check`, `config.first_call_ms`,
+`cpu_baseline` and the multi-GPU leg below -- runs only with --full.
+
+--dump-outputs DIR writes the spectrum the last timed step computed (what a caller of convolve_signal -> plain_fft
+receives) as DIR/spectrum.npy, float32 [points, 2] = (re, im), with the complex indices it holds as
+DIR/spectrum_index.npy, float64: the whole output up to 2^21 points, above that a fixed, seeded sample of 2^21 of them.
+The inputs come from seeded generators, so two builds run with the same arguments can be compared output for output.
+
+With --full, whenever the ranks form a process group (N > 1, or --init-dist) the DEFAULT mode also runs and VERIFIES the
+path's one multi-GPU exchange after the timed region: a C5-shaped batch goes out from rank 0 in chunks over grouped
+point-to-point sends, every rank convolves + transforms, the spectra come back, and rank 0 compares the first and last
+chunk of every peer bit for bit with its own computation (`c5_end_to_end`: ms, Msamples_s, verified_rows, peers; a mismatch exits 3; a
 leg that hangs is given up after --e2e-timeout and reported in the line).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full):
   value_windows the noise floor: window 0 is the contract's timed region (`value`), nine more windows of the same K steps
                 follow back to back; min / median / max of the ten values and per-window kernel times, clock and power.
   roofline      the dominant kernel (the fused overlap-save launch): algorithmic bytes per launch
@@ -59,8 +70,13 @@ C5_VECTORS_PER_GPU = 64
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="ranks = GPUs of this node (default: WORLD_SIZE, else 1)")
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: cold figure, per-kernel timings and "
+                         "roofline, value_windows, self_check, first-call cost, CPU baseline, the verified multi-GPU leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's spectrum (or a fixed, seeded sample of it) as DIR/*.npy")
     ap.add_argument("--mode", choices=("headline", "c5"), default="headline")
     ap.add_argument("--prewarm", type=float, default=0.3, help="seconds of untimed load before the warm-up steps (clock ramp; round 5: 0.15 -> 0.3 s, the ten 20-step windows of a run still climbed by 2 % after 0.15 s)")
     ap.add_argument("--points", type=int, default=None)
@@ -93,7 +109,10 @@ def parse(argv=None):
     ap.add_argument("--test-share-gpu", action="store_true",
                     help="TEST HOOK, needs BDSP_BENCH_SHARE_GPU=1 as well: all ranks on GPU 0, control collectives over gloo; "
                          "the line is marked test_hook and carries no `value`")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------ launcher
@@ -481,6 +500,33 @@ def first_call_cost(points, taps):
     except (OSError, subprocess.SubprocessError, ValueError) as e:
         return {"error": str(e)[-300:]}
 
+# ------------------------------------------------------------------------------------------ outputs of the timed path
+DUMP_MAX_POINTS = 1 << 21  # complex points written by --dump-outputs: 16 MiB of float32 (the 16M-point spectrum is 128 MiB)
+DUMP_SEED = 20160117
+
+
+def dump_outputs(dirname, torch, spec):
+    """--dump-outputs: `spec` is the last timed step's spectrum (interleaved complex f32 on the device, all vectors of the
+    batch one after the other).  Writes DIR/spectrum.npy (float32, [k, 2] = re, im) and DIR/spectrum_index.npy (float64,
+    the k complex indices): every point up to DUMP_MAX_POINTS, above that a fixed, seeded sample of DUMP_MAX_POINTS of
+    them, one at a seeded offset in every stride of total // DUMP_MAX_POINTS points -- the same indices for the same
+    arguments in every run.  Returns what was written, for the JSON line."""
+    import numpy as np
+    total = spec.numel() // 2
+    if total <= DUMP_MAX_POINTS:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        stride = total // DUMP_MAX_POINTS
+        offsets = np.random.default_rng(DUMP_SEED).integers(0, stride, size=DUMP_MAX_POINTS, dtype=np.int64)
+        idx = np.arange(DUMP_MAX_POINTS, dtype=np.int64) * stride + offsets
+    sel = torch.from_numpy(idx).to(spec.device)
+    vals = spec.view(-1, 2).index_select(0, sel).cpu().numpy().astype(np.float32)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "spectrum.npy"), vals)
+    np.save(os.path.join(dirname, "spectrum_index.npy"), idx.astype(np.float64))
+    return {"dir": dirname, "spectrum": list(vals.shape), "sampled": bool(total > DUMP_MAX_POINTS), "points_total": total}
+
+
 # ------------------------------------------------------------------------------------------ self-check of the timed output
 EXIT_SELF_CHECK, EXIT_E2E = 5, 4  # after the JSON line is out: the step's output is wrong / the multi-GPU leg hung or failed
 
@@ -599,8 +645,9 @@ def run_rank(args):
     bd._lib.check(lib.bdsp_hip_set_device(local_rank), "set_device")
     bd.require_gpu()
 
+    full = args.full
     props = torch.cuda.get_device_properties(local_rank)
-    smi = GpuSampler(getattr(props, "pci_bus_id", None), getattr(props, "pci_device_id", None)).start() if rank == 0 else None
+    smi = GpuSampler(getattr(props, "pci_bus_id", None), getattr(props, "pci_device_id", None)).start() if rank == 0 and full else None
 
     c5 = args.mode == "c5"
     n = args.points or (C5_POINTS if c5 else POINTS)
@@ -633,7 +680,7 @@ def run_rank(args):
         if ev:
             lib.bdsp_hip_event_record(ev[2], sp)
 
-    # per-kernel durations come from HIP events inside the timed region; an event record costs about 2 us of stream
+    # per-kernel durations (--full) come from HIP events inside the timed region; an event record costs about 2 us of stream
     # time, so only every `ev_stride`-th step carries the three events (at least five steps do)
     ev_stride = max(1, min(8, args.steps // 5))
     ms = C.c_float(0)
@@ -641,7 +688,7 @@ def run_rank(args):
     def timed_window():
         """EXACTLY --steps steps between barrier + synchronize on both sides (the contract's timed region; the further
         windows of `value_windows` repeat it).  Returns (seconds on this rank, t0, t_end, event deltas conv / fft in ms)."""
-        events = {i: [lib.bdsp_hip_event_create() for _ in range(3)] for i in range(0, args.steps, ev_stride)}
+        events = {i: [lib.bdsp_hip_event_create() for _ in range(3)] for i in range(0, args.steps, ev_stride)} if full else {}
         if use_dist:
             dist.barrier()
         torch.cuda.synchronize()
@@ -666,17 +713,19 @@ def run_rank(args):
     # Untimed clock pre-warm: the GPU idles at a few hundred MHz and needs tens of milliseconds of load to reach its
     # sustained clock (*measured*: the same step runs 233 us right after start-up and 216 us once the clock has
     # settled).  Then the W warm-up steps of the contract.
-    # ... but first the COLD figure a caller's first milliseconds see: three steps to load the code objects and fill the
-    # workspace cache, a short idle, then twenty timed steps from the idle clock
+    # ... but first three steps to load the code objects and fill the workspace cache, and (--full) the COLD figure a
+    # caller's first milliseconds see: a short idle, then twenty timed steps from the idle clock
     for i in range(3):
         step(i)
     torch.cuda.synchronize()
-    time.sleep(0.05)
-    t_cold = time.perf_counter()
-    for i in range(20):
-        step(i)
-    torch.cuda.synchronize()
-    cold_ms = (time.perf_counter() - t_cold) / 20 * 1e3
+    cold_ms = None
+    if full:
+        time.sleep(0.05)
+        t_cold = time.perf_counter()
+        for i in range(20):
+            step(i)
+        torch.cuda.synchronize()
+        cold_ms = (time.perf_counter() - t_cold) / 20 * 1e3
     t_pre = time.perf_counter()
     pre = 0
     while time.perf_counter() - t_pre < args.prewarm:
@@ -690,9 +739,13 @@ def run_rank(args):
     torch.cuda.synchronize()
     # ---- the contract's timed region: `value`, `ms_per_step`, `roofline` come from THIS window only
     elapsed, t0, t_end, conv_ms, fft_ms = timed_window()
-    # ---- the noise floor (round 5): further windows of the same K steps, back to back, same barriers.  r03 -> r04 moved
-    # the headline by -2.9 % on identical kernel sources and the record could not say whether that was noise.
-    more = [timed_window() for _ in range(max(0, args.windows))]
+    # ---- --dump-outputs: what the last timed step computed (rank 0), before anything else runs on the buffers
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, torch, scratch if in_scratch.value else y)
+    # ---- the noise floor (round 5, --full): further windows of the same K steps, back to back, same barriers.  r03 -> r04
+    # moved the headline by -2.9 % on identical kernel sources and the record could not say whether that was noise.
+    more = [timed_window() for _ in range(max(0, args.windows))] if full else []
     win_elapsed = [elapsed] + [w[0] for w in more]
     own_elapsed = [elapsed]  # every rank's OWN window-0 time (value_by_rank: a straggling GPU must be visible in a weak-scaling sum)
     if use_dist:
@@ -704,34 +757,34 @@ def run_rank(args):
         own_elapsed = [float(v) for v in own.tolist()]
         win_elapsed = [float(v) for v in t.tolist()]
         elapsed = win_elapsed[0]
-    steps_with_events = len(conv_ms)
+    # ---- per-kernel durations from the events of window 0 (--full)
+    if full:
+        steps_with_events = len(conv_ms)
+        # what an event pair costs by itself on this stream (two records with nothing between): the per-kernel durations
+        # below are event deltas minus this, so they are comparable with rocprofv3's kernel-only durations
+        empty = []
+        for _ in range(20):
+            ea, eb = lib.bdsp_hip_event_create(), lib.bdsp_hip_event_create()
+            lib.bdsp_hip_event_record(ea, sp)
+            lib.bdsp_hip_event_record(eb, sp)
+            lib.bdsp_hip_synchronize(sp)
+            lib.bdsp_hip_event_elapsed_ms(ea, eb, C.byref(ms))
+            empty.append(ms.value)
+            lib.bdsp_hip_event_destroy(ea)
+            lib.bdsp_hip_event_destroy(eb)
+        # (the smallest of the twenty: a pair recorded on a stream that has just gone idle can cost several times the 4-5 us a
+        # pair costs between kernels -- *measured* 18 us medians after a 200-step run -- and would be over-subtracted)
+        event_overhead = min(empty)
+        conv_raw = sum(conv_ms) / len(conv_ms)
+        conv_avg = max(conv_raw - event_overhead, 1e-6)
+        fft_avg = max(sum(fft_ms) / len(fft_ms) - event_overhead, 1e-6)
 
-    # what an event pair costs by itself on this stream (two records with nothing between): the per-kernel durations
-    # below are event deltas minus this, so they are comparable with rocprofv3's kernel-only durations
-    empty = []
-    for _ in range(20):
-        ea, eb = lib.bdsp_hip_event_create(), lib.bdsp_hip_event_create()
-        lib.bdsp_hip_event_record(ea, sp)
-        lib.bdsp_hip_event_record(eb, sp)
-        lib.bdsp_hip_synchronize(sp)
-        lib.bdsp_hip_event_elapsed_ms(ea, eb, C.byref(ms))
-        empty.append(ms.value)
-        lib.bdsp_hip_event_destroy(ea)
-        lib.bdsp_hip_event_destroy(eb)
-    # (the smallest of the twenty: a pair recorded on a stream that has just gone idle can cost several times the 4-5 us a
-    # pair costs between kernels -- *measured* 18 us medians after a 200-step run -- and would be over-subtracted)
-    event_overhead = min(empty)
-
-    conv_raw = sum(conv_ms) / len(conv_ms)
-    conv_avg = max(conv_raw - event_overhead, 1e-6)
-    fft_avg = max(sum(fft_ms) / len(fft_ms) - event_overhead, 1e-6)
-
-    # ---- the self-check (round 6): the line certifies the output of the step it timed.  The last step of the last window
-    # read xs[(K-1) % buffers]; its spectrum is still in y / scratch.  The convolution result it transformed is gone (the
+    # ---- the self-check (round 6, --full): the line certifies the output of the step it timed.  The last step of the last
+    # window read xs[(K-1) % buffers]; its spectrum is still in y / scratch.  The convolution result it transformed is gone (the
     # passes ping-pong through y), so that step runs ONCE more, untimed, on the same input: its spectrum must equal the
     # timed one bit for bit (same kernels, same data), and its y is what the checker sees.
     check = None
-    if rank == 0 and not args.no_self_check:
+    if rank == 0 and full and not args.no_self_check:
         import numpy as np
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as orc
@@ -759,6 +812,46 @@ def run_rank(args):
     out = None
     if rank == 0:
         samples = n * nvec * world * args.steps
+        if c5:
+            workload = ("c5: %d vectors of %d complex f32 points per GPU (%d in all), batched convolve_signal(%d taps, fused "
+                        "overlap-save) -> plain_fft; value = compute only, shards resident" % (nvec, n, nvec * world, m))
+        else:
+            workload = ("c3+fft16m: convolve_signal(%d-pt complex f32, %d complex taps, fused overlap-save) -> "
+                        "plain_fft(%d-pt), one vector per GPU" % (n, m, n))
+        out = {
+            "metric": ("Msamples/s for f32 complex FFT + overlap-save conv, 16M-pt" if not c5 else
+                       "Msamples/s for f32 complex FFT + overlap-save conv, batch of %d x %d-pt vectors per GPU (BASELINE config C5)" % (nvec, n)),
+            "value": None if share_gpu else samples / elapsed / 1e6,
+            "unit": "Msamples/s",
+            "n_gpus": world,
+            "ranks_seen": ranks_seen,
+            # each rank's own rate over window 0 (its own clock between the same two barriers); `value` divides ALL ranks'
+            # samples by the slowest rank's time
+            "value_by_rank": None if share_gpu else [n * nvec * args.steps / e / 1e6 for e in own_elapsed],
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "full": full,
+            "config": {
+                "workload": workload,
+                "points": n, "taps": m, "vectors_per_gpu": nvec, "input_buffers_rotated": len(xs),
+                "untimed_clock_prewarm_s": args.prewarm, "untimed_prewarm_steps": pre,
+                "parallelism": "independent vectors per GPU, no data-path collective" + (
+                    " -- TEST HOOK BDSP_BENCH_SHARE_GPU: all ranks on GPU 0, control collectives over gloo" if share_gpu else ""),
+            },
+        }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
+        if share_gpu:
+            out["test_hook"] = True
+            out["test_hook_value"] = samples / elapsed / 1e6
+    # ---- --full: per-kernel figures and roofline of window 0, clock / power, the noise floor, first-call cost, self-check
+    if rank == 0 and full:
         win_values = [samples / e / 1e6 for e in win_elapsed]
         sv = sorted(win_values)
         win_spans = [(t0, t_end)] + [(w[1], w[2]) for w in more]
@@ -799,91 +892,61 @@ def run_rank(args):
         first_call = None
         if world == 1 and not c5 and not args.no_first_call:
             first_call = first_call_cost(n, m)
-        if c5:
-            workload = ("c5: %d vectors of %d complex f32 points per GPU (%d in all), batched convolve_signal(%d taps, fused "
-                        "overlap-save) -> plain_fft; value = compute only, shards resident" % (nvec, n, nvec * world, m))
-        else:
-            workload = ("c3+fft16m: convolve_signal(%d-pt complex f32, %d complex taps, fused overlap-save) -> "
-                        "plain_fft(%d-pt), one vector per GPU" % (n, m, n))
-        out = {
-            "metric": ("Msamples/s for f32 complex FFT + overlap-save conv, 16M-pt" if not c5 else
-                       "Msamples/s for f32 complex FFT + overlap-save conv, batch of %d x %d-pt vectors per GPU (BASELINE config C5)" % (nvec, n)),
-            "value": None if share_gpu else samples / elapsed / 1e6,
-            "unit": "Msamples/s",
-            "n_gpus": world,
-            "ranks_seen": ranks_seen,
-            # each rank's own rate over window 0 (its own clock between the same two barriers); `value` divides ALL ranks'
-            # samples by the slowest rank's time
-            "value_by_rank": None if share_gpu else [n * nvec * args.steps / e / 1e6 for e in own_elapsed],
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {
-                "workload": workload,
-                "points": n, "taps": m, "vectors_per_gpu": nvec, "input_buffers_rotated": len(xs),
-                "untimed_clock_prewarm_s": args.prewarm, "untimed_prewarm_steps": pre,
-                "cold_ms_per_step_first_20_steps_after_idle": cold_ms,
-                # a fresh process's first plain_fft / convolve_signal against its second and third
-                "first_call_ms": first_call,
-                "steps_with_kernel_events": steps_with_events,
-                "parallelism": "independent vectors per GPU, no data-path collective" + (
-                    " -- TEST HOOK BDSP_BENCH_SHARE_GPU: all ranks on GPU 0, control collectives over gloo" if share_gpu else ""),
-            },
-            "roofline": {
-                "kernel": "k_overlap_save_v2<R0=4> (fused load->FFT4096->xH->IFFT4096->store)",
-                "bound": "hbm",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "traffic": prof.get("conv_traffic"),
-                "algorithmic_bytes_per_launch": algo_bytes,
-                "avg_launch_ms": conv_avg,
-                "event_delta_ms": conv_raw, "event_pair_overhead_ms": event_overhead,
-                # clock and socket power of THIS run (host thread polling librocm_smi64 during the untimed pre-warm -- the
-                # same load as the timed steps, tens of samples -- and during the timed region itself); `limited_by` is a
-                # sentence DERIVED from them or null, never a remembered measurement
-                "sclk_mhz": clk["timed"]["sclk_mhz"] if clk["timed"]["sclk_mhz"] is not None else clk["prewarm"]["sclk_mhz"],
-                "socket_power_w": clk["timed"]["socket_power_w"] if clk["timed"]["socket_power_w"] is not None else clk["prewarm"]["socket_power_w"],
-                "power_cap_w": clk["power_cap_w"], "sclk_max_mhz": clk["sclk_max_mhz"],
-                "clock_power_samples": clk,
-                "limited_by": clk["limited_by"],
-                # the same achieved rate against the 6.29 TB/s a float4 copy reaches on this chip
-                "frac_vs_achievable": achieved / HBM_ACHIEVABLE_GBS,
-                "dominant_per_launch": bool(conv_avg >= fft_avg / passes),
-                "share_of_step": conv_avg / (conv_avg + fft_avg),
-                # the kernel with the largest share of the STEP and ITS fraction, so that `frac` above (the fused block
-                # kernel, the dominant kernel per launch) cannot be read as the step's
-                "dominant_by_time": dominant_by_time,
-                # the whole step and the transform, in the same terms (algorithmic bytes: 32 B per sample for the step,
-                # 16 B per sample for the transform whatever its number of passes) -- the block kernel is a third of the step
-                "step_frac": step_algo_gbs / HBM_PEAK_GBS,
-                "step_frac_vs_achievable": step_algo_gbs / HBM_ACHIEVABLE_GBS,
-                "fft_frac_algorithmic": fft_algo_gbs / HBM_PEAK_GBS,
-                "fft_passes": passes,
-                # HBM bytes the transform's passes moved per algorithmic byte (PMC, profiles/) -- 3.0 = three full trips
-                "fft_traffic_ratio": (prof["fft_traffic"] / (16.0 * n * nvec)) if prof.get("fft_traffic") else None,
-                # the same fraction from the committed rocprofv3 kernel trace of this command (average over ALL launches
-                # incl. the clock ramp and the cold steps, and the fastest launch)
-                "frac_rocprof": (algo_bytes / (prof["conv_avg_ns"] * 1e-9) / 1e9 / HBM_PEAK_GBS) if prof.get("conv_avg_ns") else None,
-                "frac_rocprof_min_launch": (algo_bytes / (prof["conv_min_ns"] * 1e-9) / 1e9 / HBM_PEAK_GBS) if prof.get("conv_min_ns") else None,
-                "profile": ("profiles/%s_* (%s)" % (PROFILE_TAG, "collected on these kernel sources" if prof.get("stale") is False else
-                            ("STALE: collected on other kernel sources, figures withheld" if prof.get("stale") else "missing"))) if headline else None,
-            },
-            "kernels": {
-                "conv_ms": conv_avg, "conv_Msamples_s": n * nvec / (conv_avg * 1e-3) / 1e6,
-                "fft_ms": fft_avg, "fft_Msamples_s": n * nvec / (fft_avg * 1e-3) / 1e6,
-                "fft_passes": passes,
-                "fft_achieved_algorithmic_GBs": fft_algo_gbs,
-                "fft_achieved_pass_adjusted_GBs": fft_algo_gbs * passes,
-                "fft_frac_of_roofline_algorithmic": fft_algo_gbs / HBM_PEAK_GBS,
-                "step_frac_of_roofline_algorithmic": step_algo_gbs / HBM_PEAK_GBS,
-            },
+        out["config"].update({
+            "cold_ms_per_step_first_20_steps_after_idle": cold_ms,
+            # a fresh process's first plain_fft / convolve_signal against its second and third
+            "first_call_ms": first_call,
+            "steps_with_kernel_events": steps_with_events,
+        })
+        out["roofline"] = {
+            "kernel": "k_overlap_save_v2<R0=4> (fused load->FFT4096->xH->IFFT4096->store)",
+            "bound": "hbm",
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS,
+            "traffic": prof.get("conv_traffic"),
+            "algorithmic_bytes_per_launch": algo_bytes,
+            "avg_launch_ms": conv_avg,
+            "event_delta_ms": conv_raw, "event_pair_overhead_ms": event_overhead,
+            # clock and socket power of THIS run (host thread polling librocm_smi64 during the untimed pre-warm -- the
+            # same load as the timed steps, tens of samples -- and during the timed region itself); `limited_by` is a
+            # sentence DERIVED from them or null, never a remembered measurement
+            "sclk_mhz": clk["timed"]["sclk_mhz"] if clk["timed"]["sclk_mhz"] is not None else clk["prewarm"]["sclk_mhz"],
+            "socket_power_w": clk["timed"]["socket_power_w"] if clk["timed"]["socket_power_w"] is not None else clk["prewarm"]["socket_power_w"],
+            "power_cap_w": clk["power_cap_w"], "sclk_max_mhz": clk["sclk_max_mhz"],
+            "clock_power_samples": clk,
+            "limited_by": clk["limited_by"],
+            # the same achieved rate against the 6.29 TB/s a float4 copy reaches on this chip
+            "frac_vs_achievable": achieved / HBM_ACHIEVABLE_GBS,
+            "dominant_per_launch": bool(conv_avg >= fft_avg / passes),
+            "share_of_step": conv_avg / (conv_avg + fft_avg),
+            # the kernel with the largest share of the STEP and ITS fraction, so that `frac` above (the fused block
+            # kernel, the dominant kernel per launch) cannot be read as the step's
+            "dominant_by_time": dominant_by_time,
+            # the whole step and the transform, in the same terms (algorithmic bytes: 32 B per sample for the step,
+            # 16 B per sample for the transform whatever its number of passes) -- the block kernel is a third of the step
+            "step_frac": step_algo_gbs / HBM_PEAK_GBS,
+            "step_frac_vs_achievable": step_algo_gbs / HBM_ACHIEVABLE_GBS,
+            "fft_frac_algorithmic": fft_algo_gbs / HBM_PEAK_GBS,
+            "fft_passes": passes,
+            # HBM bytes the transform's passes moved per algorithmic byte (PMC, profiles/) -- 3.0 = three full trips
+            "fft_traffic_ratio": (prof["fft_traffic"] / (16.0 * n * nvec)) if prof.get("fft_traffic") else None,
+            # the same fraction from the committed rocprofv3 kernel trace of this command (average over ALL launches
+            # incl. the clock ramp and the cold steps, and the fastest launch)
+            "frac_rocprof": (algo_bytes / (prof["conv_avg_ns"] * 1e-9) / 1e9 / HBM_PEAK_GBS) if prof.get("conv_avg_ns") else None,
+            "frac_rocprof_min_launch": (algo_bytes / (prof["conv_min_ns"] * 1e-9) / 1e9 / HBM_PEAK_GBS) if prof.get("conv_min_ns") else None,
+            "profile": ("profiles/%s_* (%s)" % (PROFILE_TAG, "collected on these kernel sources" if prof.get("stale") is False else
+                        ("STALE: collected on other kernel sources, figures withheld" if prof.get("stale") else "missing"))) if headline else None,
+        }
+        out["kernels"] = {
+            "conv_ms": conv_avg, "conv_Msamples_s": n * nvec / (conv_avg * 1e-3) / 1e6,
+            "fft_ms": fft_avg, "fft_Msamples_s": n * nvec / (fft_avg * 1e-3) / 1e6,
+            "fft_passes": passes,
+            "fft_achieved_algorithmic_GBs": fft_algo_gbs,
+            "fft_achieved_pass_adjusted_GBs": fft_algo_gbs * passes,
+            "fft_frac_of_roofline_algorithmic": fft_algo_gbs / HBM_PEAK_GBS,
+            "step_frac_of_roofline_algorithmic": step_algo_gbs / HBM_PEAK_GBS,
         }
         # the noise floor: window 0 IS the contract's timed region (`value`), windows 1.. repeat it back to back
         wclk = [smi.window(a, b) if smi is not None else {"samples": 0, "sclk_mhz": None, "socket_power_w": None} for a, b in win_spans]
@@ -900,12 +963,9 @@ def run_rank(args):
             "sampler_period_ms": 0.5,
         }
         out["self_check"] = check
-        if share_gpu:
-            out["test_hook"] = True
-            out["test_hook_value"] = samples / elapsed / 1e6
 
-    # ---- the path's multi-GPU exchange, AFTER every figure of the line above is final and under a watchdog: a leg that
-    # hangs in a collective must not cost the record the measurements that were complete before it started
+    # ---- the path's multi-GPU exchange (--full), AFTER every figure of the line above is final and under a watchdog: a leg
+    # that hangs in a collective must not cost the record the measurements that were complete before it started
     def e2e_leg():
         if c5 and not (share_gpu and world > 1):  # (the chunked scatter/gather sends device tensors: RCCL only)
             return c5_end_to_end(args, bd, torch, dist, dev, rank, world, n, m, nvec, use_dist)
@@ -915,12 +975,12 @@ def run_rank(args):
             return verified_scatter_gather(args, torch, dist, dev, rank, world, m, share_gpu)
         return None
 
-    e2e, group_ok = guarded_leg(e2e_leg, args.e2e_timeout, rank, out)
+    e2e, group_ok = guarded_leg(e2e_leg, args.e2e_timeout, rank, out) if full else (None, True)
 
     if rank == 0:
         if e2e is not None:
             out["c5_end_to_end"] = e2e
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(n, m, args.cpu_sample_points, nvec if c5 else 1)
         print(json.dumps(out))
         sys.stdout.flush()

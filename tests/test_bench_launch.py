@@ -153,3 +153,39 @@ def test_clock_power_sampler_degrades_to_nulls_without_a_device():
         assert w == {"samples": 0, "sclk_mhz": None, "socket_power_w": None} and s.cap_w is None
     else:  # (a box with a GPU: real samples)
         assert w["samples"] >= 1
+
+
+def test_full_is_off_by_default_and_steps_must_be_positive():
+    """A plain run is the lean one (the extra measurements and checks need --full); --steps sets the timed steps."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    p = subprocess.run([sys.executable, BENCH, "--steps", "0"], env=_env(), capture_output=True, text=True, timeout=60)
+    assert p.returncode != 0 and "--steps" in p.stderr
+
+
+def test_dump_outputs_writes_the_whole_output_or_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs on a host tensor standing in for the spectrum: every point while the output is small, above the cap
+    the same seeded sample of indices in every run; float32 values, float64 indices."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    spec = torch.arange(2 * 1000, dtype=torch.float32)  # interleaved (re, im) of 1000 points: re = 2 i, im = 2 i + 1
+    info = bench.dump_outputs(str(tmp_path / "whole"), torch, spec)
+    vals, idx = np.load(str(tmp_path / "whole" / "spectrum.npy")), np.load(str(tmp_path / "whole" / "spectrum_index.npy"))
+    assert vals.dtype == np.float32 and idx.dtype == np.float64 and vals.shape == (1000, 2)
+    assert np.array_equal(idx, np.arange(1000)) and np.array_equal(vals.ravel(), spec.numpy())
+    assert info["sampled"] is False and info["points_total"] == 1000
+    monkeypatch.setattr(bench, "DUMP_MAX_POINTS", 100)
+    for run in ("a", "b"):
+        info = bench.dump_outputs(str(tmp_path / run), torch, spec)
+        assert info["sampled"] is True
+    va, ia = np.load(str(tmp_path / "a" / "spectrum.npy")), np.load(str(tmp_path / "a" / "spectrum_index.npy"))
+    vb, ib = np.load(str(tmp_path / "b" / "spectrum.npy")), np.load(str(tmp_path / "b" / "spectrum_index.npy"))
+    assert np.array_equal(ia, ib) and np.array_equal(va, vb)
+    assert ia.size == 100 and np.all(np.diff(ia) > 0) and ia[-1] < 1000 and np.all(ia // 10 == np.arange(100))
+    assert np.array_equal(va[:, 0], 2 * ia) and np.array_equal(va[:, 1], 2 * ia + 1)

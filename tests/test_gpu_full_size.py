@@ -401,14 +401,14 @@ def test_f64_and_real_convolution_4m_whole_output():
 
 @pytest.mark.gpu
 def test_bench_py_runs_both_modes_and_prints_the_contract_fields():
-    """bench.py end to end on this GPU (few steps): the headline mode and --mode c5, one JSON line each with the
+    """bench.py --full end to end on this GPU (few steps): the headline mode and --mode c5, one JSON line each with the
     contract's fields, `roofline` and (headline) `cpu_baseline`; `--gpus 1` is accepted as the driver passes it."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "16", "--warmup", "2",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "16", "--warmup", "2", "--full",
                         "--prewarm", "0.02", "--cpu-sample-points", str(1 << 18)], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads(p.stdout.strip().splitlines()[-1])
@@ -463,16 +463,16 @@ def test_bench_py_runs_both_modes_and_prints_the_contract_fields():
     assert d["value_by_rank"] == [d["value"]]
     # ... and a wrong output makes the run fail AFTER the line is printed (test hook: one value of the checked y is changed)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "1", "--prewarm", "0.02", "--windows", "0",
-                        "--no-cpu-baseline", "--no-first-call", "--test-corrupt-self-check"], env=dict(env, BDSP_BENCH_CORRUPT_SELF_CHECK="1"),
+                        "--full", "--no-cpu-baseline", "--no-first-call", "--test-corrupt-self-check"], env=dict(env, BDSP_BENCH_CORRUPT_SELF_CHECK="1"),
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 5 and "self-check FAILED" in p.stderr, (p.returncode, p.stderr[-1500:])
     bad = json.loads(p.stdout.strip().splitlines()[-1])["self_check"]
     assert bad["ok"] is False and bad["conv_rel_l2_max"] > 1e-3 and bad["rerun_spectrum_bit_identical_to_timed"] is True
     # (the flag alone, without the environment variable, changes nothing; --no-self-check leaves the key null)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "1", "--prewarm", "0.02", "--windows", "0",
-                        "--no-cpu-baseline", "--no-first-call", "--no-self-check"], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline", "--no-first-call", "--no-self-check"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0 and json.loads(p.stdout.strip().splitlines()[-1])["self_check"] is None
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--mode", "c5", "--steps", "4", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--mode", "c5", "--steps", "4", "--warmup", "1", "--full",
                         "--prewarm", "0.02", "--vectors-per-gpu", "16", "--no-cpu-baseline"], env=env, capture_output=True,
                        text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -480,6 +480,46 @@ def test_bench_py_runs_both_modes_and_prints_the_contract_fields():
     assert d["config"]["vectors_per_gpu"] == 16 and d["c5_end_to_end"]["vectors"] == 16 and d["c5_end_to_end"]["ms"] > 0
     assert d["c5_end_to_end"]["expected_ms"] is None  # (world size 1: nothing travels)
     assert d["self_check"]["ok"] is True and d["self_check"]["vector_checked"] == 15, d["self_check"]
+
+
+@pytest.mark.gpu
+def test_bench_py_plain_run_is_lean_and_dumps_the_last_timed_output(tmp_path):
+    """A plain run (no --full) prints the contract's fields and nothing that needs runs of its own; --dump-outputs writes
+    the last timed step's spectrum -- a fixed sample of the 16M points -- and two runs with the same arguments write the
+    same bits.  A c5 batch of 2 x 2^20 points is small enough to be written whole."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    lines = []
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                            "--prewarm", "0.02", "--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines.append(json.loads(p.stdout.strip().splitlines()[-1]))
+    d = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus", "config"):
+        assert k in d, k
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["full"] is False and d["value"] > 1000 and d["ms_per_step"] > 0
+    assert abs(d["value"] - (1 << 24) * 7 / (d["ms_per_step"] * 7e-3) / 1e6) < 1e-6 * d["value"]
+    for k in ("roofline", "kernels", "value_windows", "self_check", "cpu_baseline", "c5_end_to_end"):
+        assert k not in d, k
+    assert "first_call_ms" not in d["config"] and "cold_ms_per_step_first_20_steps_after_idle" not in d["config"]
+    spec = [np.load(str(tmp_path / run / "spectrum.npy")) for run in ("a", "b")]
+    idx = [np.load(str(tmp_path / run / "spectrum_index.npy")) for run in ("a", "b")]
+    assert spec[0].dtype == np.float32 and idx[0].dtype == np.float64 and spec[0].shape == (idx[0].shape[0], 2)
+    assert idx[0].shape[0] == 1 << 21 and np.all(np.diff(idx[0]) > 0) and idx[0][-1] < 1 << 24
+    assert d["dump_outputs"]["sampled"] is True and d["dump_outputs"]["spectrum"] == list(spec[0].shape)
+    assert np.array_equal(idx[0], idx[1]) and np.array_equal(spec[0], spec[1]) and np.all(np.isfinite(spec[0]))
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--mode", "c5", "--vectors-per-gpu", "2", "--steps", "3",
+                        "--warmup", "1", "--prewarm", "0.02", "--dump-outputs", str(tmp_path / "c5")],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads(p.stdout.strip().splitlines()[-1])
+    assert "c5_end_to_end" not in d and d["dump_outputs"]["sampled"] is False
+    idx = np.load(str(tmp_path / "c5" / "spectrum_index.npy"))
+    assert np.array_equal(idx, np.arange(2 << 20, dtype=np.float64)) and np.load(str(tmp_path / "c5" / "spectrum.npy")).shape == (2 << 20, 2)
 
 
 def test_bench_py_two_and_three_ranks_through_its_own_launcher_on_one_gpu():
@@ -504,7 +544,7 @@ def test_bench_py_two_and_three_ranks_through_its_own_launcher_on_one_gpu():
     for ranks in (1, 2, 3):
         # the environment variable ALONE must change nothing (ranks == 1 runs without the flag: a plain line with a value)
         hook = ["--test-share-gpu"] if ranks > 1 else []
-        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--steps", "30", "--warmup", "3",
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--steps", "30", "--warmup", "3", "--full",
                             "--prewarm", "0.05", "--no-cpu-baseline", "--e2e-vectors-per-gpu", "4"] + hook, env=env, capture_output=True, text=True, timeout=600)
         assert p.returncode == 0, (ranks, p.stderr[-2000:])
         lines = [l for l in p.stdout.strip().splitlines() if l.startswith("{")]
@@ -532,13 +572,13 @@ def test_bench_py_two_and_three_ranks_through_its_own_launcher_on_one_gpu():
             assert d["value_windows"]["values"] is None and len(d["value_windows"]["ms_per_step"]) == 10
     # ... and a gathered row that differs from rank 0's own computation ends every rank non-zero
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--prewarm", "0.02",
-                        "--no-cpu-baseline", "--test-share-gpu", "--e2e-vectors-per-gpu", "4", "--windows", "1"],
+                        "--full", "--no-cpu-baseline", "--test-share-gpu", "--e2e-vectors-per-gpu", "4", "--windows", "1"],
                        env=dict(env, BDSP_BENCH_CORRUPT_E2E="1"), capture_output=True, text=True, timeout=600)
     assert p.returncode != 0 and "differ from rank 0's own computation" in p.stderr, (p.returncode, p.stderr[-1500:])
     # ... and a leg that HANGS (a rank never joins it) does not cost the record its measurements: after --e2e-timeout rank 0
     # prints the line -- every other figure was final before the leg started -- with an error in the leg's place
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--prewarm", "0.02",
-                        "--no-cpu-baseline", "--test-share-gpu", "--e2e-vectors-per-gpu", "4", "--windows", "1", "--e2e-timeout", "20"],
+                        "--full", "--no-cpu-baseline", "--test-share-gpu", "--e2e-vectors-per-gpu", "4", "--windows", "1", "--e2e-timeout", "20"],
                        env=dict(env, BDSP_BENCH_HANG_E2E="1"), capture_output=True, text=True, timeout=600)
     lines = [l for l in p.stdout.strip().splitlines() if l.startswith("{")]
     # (round 6: the ranks leave with exit code 4 AFTER the line, so the launcher -- and the driver -- see the failure)
@@ -762,7 +802,7 @@ def test_rccl_runs_on_the_one_gpu_at_world_size_one(tmp_path):
     assert p.returncode == 0 and "RCCL_WS1_OK" in p.stdout, (p.stdout[-1500:], p.stderr[-3000:])
     for extra in ([], ["--mode", "c5", "--vectors-per-gpu", "16"]):
         p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--init-dist", "--steps", "8", "--warmup", "2",
-                            "--prewarm", "0.02", "--no-cpu-baseline"] + extra, env=env_for_child(), capture_output=True, text=True, timeout=600)
+                            "--full", "--prewarm", "0.02", "--no-cpu-baseline"] + extra, env=env_for_child(), capture_output=True, text=True, timeout=600)
         assert p.returncode == 0, (extra, p.stderr[-3000:])
         d = json.loads([l for l in p.stdout.strip().splitlines() if l.startswith("{")][-1])
         assert d["n_gpus"] == 1 and d["ranks_seen"] == 1 and d["value"] > 1000

@@ -9,13 +9,13 @@ OUT=$ROOT/gpurun_out/${TAG}prof
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # --- the bench step: kernel trace + stats
-$RP --kernel-trace --stats --output-format csv -d $OUT/bench_stats -o bench -- python3 $ROOT/bench.py --no-cpu-baseline --no-first-call --no-self-check > $OUT/bench_line_under_rocprof.json 2> $OUT/bench_stats.err
+$RP --kernel-trace --stats --output-format csv -d $OUT/bench_stats -o bench -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-first-call --no-self-check > $OUT/bench_line_under_rocprof.json 2> $OUT/bench_stats.err
 # --- the bench step: PMC (separate passes, no trace domains besides the kernel trace)
 pmc() { # outdir name script args -- counters
   dir=$1; name=$2; shift 2
   $RP --kernel-trace --pmc "$@" --output-format csv -d $OUT/$dir -o $name -- python3 $PMC_SCRIPT $PMC_ARGS > $OUT/$dir.$name.log 2>&1
 }
-PMC_SCRIPT=$ROOT/bench.py; PMC_ARGS="--steps 3 --warmup 1 --prewarm 0.02 --no-cpu-baseline --no-first-call --no-self-check"
+PMC_SCRIPT=$ROOT/bench.py; PMC_ARGS="--full --steps 3 --warmup 1 --prewarm 0.02 --no-cpu-baseline --no-first-call --no-self-check"
 pmc bench_pmc sq1 SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE
 pmc bench_pmc sq2 SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_WAVES SQ_BUSY_CYCLES SQ_WAIT_INST_LDS
 pmc bench_pmc fetch FETCH_SIZE GRBM_GUI_ACTIVE
