@@ -278,6 +278,20 @@ for _s, _t, _R in (("32", _F, VectorInteropResult32), ("64", _D, VectorInteropRe
     _proto(_m + "convolve_signal_mat" + _s, C.c_int32, _P, C.POINTER(_P), _SZ)
     _proto(_m + "interpolatef" + _s, C.c_int32, _P, C.c_int32, _t, _t, _t, _SZ)
     _proto(_m + "multiply_frequency_response" + _s, C.c_int32, _P, C.c_int32, _t, _t)
+    # per-row statistics, sums, dot products: (matrix, out array, out length[, split length])
+    for _n, _o in (("real_statistics", _ST), ("complex_statistics", _CST), ("real_statistics_prec", Statistics64),
+                   ("complex_statistics_prec", ComplexStatistics64), ("real_sum", _t), ("real_sum_sq", _t),
+                   ("real_sum_prec", _D), ("real_sum_sq_prec", _D), ("complex_sum", _CX), ("complex_sum_sq", _CX),
+                   ("complex_sum_prec", Complex64), ("complex_sum_sq_prec", Complex64)):
+        _proto(_m + _n + _s, C.c_int32, _P, C.POINTER(_o), _SZ)
+    for _n, _o in (("real_statistics_split", _ST), ("complex_statistics_split", _CST),
+                   ("real_statistics_split_prec", Statistics64), ("complex_statistics_split_prec", ComplexStatistics64)):
+        _proto(_m + _n + _s, C.c_int32, _P, C.POINTER(_o), _SZ, _SZ)
+    for _v in ("", "_vector"):
+        for _n, _o in (("real", _t), ("complex", _CX)):
+            _proto(_m + _n + "_dot_product" + _v + _s, C.c_int32, _P, _P, C.POINTER(_o), _SZ)
+            _proto(_m + _n + "_dot_product" + _v + "_prec" + _s, C.c_int32, _P, _P,
+                   C.POINTER(_D if _n == "real" else Complex64), _SZ)
 
 WINDOW_FN32 = C.CFUNCTYPE(_F, _P, _SZ, _SZ)
 WINDOW_FN64 = C.CFUNCTYPE(_D, _P, _SZ, _SZ)

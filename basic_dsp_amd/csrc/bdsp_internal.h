@@ -239,6 +239,29 @@ int red_stats(const T* x, size_t total, size_t buckets, bool is_complex, bool mi
 template <typename T>
 int red_dot(const T* x, const T* y, size_t count, bool is_complex, StatPartial* partials, StatPartial* out, hipStream_t s);
 
+// mat_reduce.hip -- per-row reductions of a matrix.  `out` (device) receives one result per row (row-major [row][bucket]
+// for nb > 1) in the layout `kind` names: the header's Statistics / ComplexStatistics struct in T or double, or one
+// (complex) sum / sum of squares in T or double.
+enum MrOut { MR_OUT_PARTIAL, MR_OUT_STATS, MR_OUT_STATS_PREC, MR_OUT_SUM, MR_OUT_SUM_PREC, MR_OUT_SUM_SQ, MR_OUT_SUM_SQ_PREC };
+struct MrGeom {            // one launch's work: units = rows * nb * chunks
+    size_t n;              // elements (scalars, or complex pairs) per row
+    size_t stride;         // scalars from one row to the next
+    size_t nb;             // buckets of statistics_split (1 = the whole row)
+    unsigned chunks;       // workgroups per segment (long rows)
+    size_t per;            // elements of a segment per chunk
+    size_t units;
+    int kind;
+    void* out;
+};
+// statistics / sums of `rows` rows of `n` elements (complex pairs if cplx), element j of bucket j % nb at index j / nb
+template <typename T>
+int mr_stats(const T* x, size_t rows, size_t n, size_t stride, size_t nb, bool cplx, bool minmax, int kind, void* out,
+             hipStream_t s);
+// dot products of row r of x with row r of y (ystride scalars apart; 0 = one vector for every row), n elements each
+template <typename T>
+int mr_dot(const T* x, size_t xstride, const T* y, size_t ystride, size_t rows, size_t n, bool cplx, int kind,
+           void* out, hipStream_t s);
+
 // bluestein.hip
 template <typename T> int bs_chirp(T* c, size_t n, bool inverse, hipStream_t s);
 template <typename T> int bs_kernel(const T* c, T* b, size_t n, size_t m, hipStream_t s);

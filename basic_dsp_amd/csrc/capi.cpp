@@ -1949,6 +1949,68 @@ int mat_transfer(DevMat<T>* m, T* host, const T* src, size_t len)
     return BDSP_OK;
 }
 
+// Per-row statistics / sums / dot products (matrix/src/general/statistics.rs, mod.rs:9-241): one batched device
+// pass (mat_reduce.hip) writes the finished results in `kind`'s layout to workspace, one copy hands them to the
+// caller, one synchronisation.  out_len must be rows (* nb for split); code -1 for a poisoned matrix, whose rows are
+// empty, with the results written as the vector path writes them.
+template <typename T>
+int mat_reduce_finish(const DevMat<T>* m, size_t elem_bytes, void* out, size_t out_len, WsBlock& ob, hipStream_t s)
+{
+    BDSP_HIP_TRY(hipMemcpyAsync(out, ob.p, elem_bytes * out_len, hipMemcpyDeviceToHost, s));
+    BDSP_HIP_TRY(hipStreamSynchronize(s));
+    return m->v.erroneous() ? BDSP_ERR_POISONED : BDSP_OK;
+}
+
+template <typename T>
+int mat_stats(const DevMat<T>* m, bool cplx, bool minmax, size_t nb, int kind, size_t elem_bytes, void* out,
+              size_t out_len)
+{
+    if (nb == 0) return BDSP_OK;                   // statistics_split(0): nothing to write
+    if (nb > 16) return BDSP_ERR_ARG_LENGTH;       // STATS_VEC_CAPACTIY, as stats_split
+    if (out_len != m->rows * nb) return BDSP_ERR_ARG_LENGTH;
+    if (m->rows == 0) return m->v.erroneous() ? BDSP_ERR_POISONED : BDSP_OK;
+    const size_t rl = m->row_len();
+    hipStream_t s = lib_stream();
+    WsBlock ob;
+    BDSP_TRY(ob.alloc(elem_bytes * out_len, s));
+    BDSP_TRY(mr_stats<T>(m->v.data, m->rows, cplx ? rl / 2 : rl, rl, nb, cplx, minmax, kind, ob.p, s));
+    return mat_reduce_finish<T>(m, elem_bytes, out, out_len, ob, s);
+}
+
+// row r with row r of a matrix (o_rows == rows, o_stride = its row length) or with one vector (o_stride = 0); the
+// number-space / metadata codes 4 / 3 / 2 of `dot`, then 7 for unequal row counts (stricter than the reference's zip,
+// as mat_binary) or a wrong output length; the count per row is min(row length, operand length)
+template <typename T>
+int mat_dot(const DevMat<T>* m, const DevVec<T>* o, size_t o_rows, size_t o_stride, size_t o_len, bool cplx, int kind,
+            size_t elem_bytes, void* out, size_t out_len)
+{
+    if (!cplx && m->v.complex_) return BDSP_ERR_MUST_BE_REAL;
+    if (cplx && !m->v.complex_) return BDSP_ERR_MUST_BE_COMPLEX;
+    if (cplx && (!o->complex_ || o->freq != m->v.freq)) return BDSP_ERR_META_DATA;
+    if (o_rows != m->rows || out_len != m->rows) return BDSP_ERR_ARG_LENGTH;
+    if (m->rows == 0) return m->v.erroneous() ? BDSP_ERR_POISONED : BDSP_OK;
+    const size_t rl = m->row_len(), len = rl < o_len ? rl : o_len;
+    hipStream_t s = lib_stream();
+    WsBlock ob;
+    BDSP_TRY(ob.alloc(elem_bytes * out_len, s));
+    BDSP_TRY(mr_dot<T>(m->v.data, rl, o->data, o_stride, m->rows, cplx ? len / 2 : len, cplx, kind, ob.p, s));
+    return mat_reduce_finish<T>(m, elem_bytes, out, out_len, ob, s);
+}
+
+template <typename T>
+int mat_dot_mat(const DevMat<T>* m, const DevMat<T>* o, bool cplx, int kind, size_t elem_bytes, void* out,
+                size_t out_len)
+{
+    return mat_dot<T>(m, &o->v, o->rows, o->row_len(), o->row_len(), cplx, kind, elem_bytes, out, out_len);
+}
+
+template <typename T>
+int mat_dot_vec(const DevMat<T>* m, const DevVec<T>* o, bool cplx, int kind, size_t elem_bytes, void* out,
+                size_t out_len)
+{
+    return mat_dot<T>(m, o, m->rows, 0, o->valid_len, cplx, kind, elem_bytes, out, out_len);
+}
+
 } // namespace
 
 // ==============================================================================================
@@ -2502,6 +2564,61 @@ BDSP_STATS(64, double, VecBuf64)
 BDSP_MAT(32, float, MatBuf32, VecBuf32)
 BDSP_MAT(64, double, MatBuf64, VecBuf64)
 #undef BDSP_MAT
+
+// per-row statistics, sums, dot products (mat_stats / mat_dot above)
+#define BDSP_MAT_STATS(SFX, T, MB, VB)                                                                      \
+    int32_t bdsp_hip_mat_real_statistics##SFX(const MB* m, Statistics##SFX* out, size_t len)                \
+    { return mat_stats<T>(MC##SFX(m), false, true, 1, MR_OUT_STATS, sizeof(*out), out, len); }             \
+    int32_t bdsp_hip_mat_complex_statistics##SFX(const MB* m, ComplexStatistics##SFX* out, size_t len)      \
+    { return mat_stats<T>(MC##SFX(m), true, true, 1, MR_OUT_STATS, sizeof(*out), out, len); }              \
+    int32_t bdsp_hip_mat_real_statistics_prec##SFX(const MB* m, Statistics64* out, size_t len)              \
+    { return mat_stats<T>(MC##SFX(m), false, true, 1, MR_OUT_STATS_PREC, sizeof(*out), out, len); }        \
+    int32_t bdsp_hip_mat_complex_statistics_prec##SFX(const MB* m, ComplexStatistics64* out, size_t len)    \
+    { return mat_stats<T>(MC##SFX(m), true, true, 1, MR_OUT_STATS_PREC, sizeof(*out), out, len); }         \
+    int32_t bdsp_hip_mat_real_statistics_split##SFX(const MB* m, Statistics##SFX* out, size_t out_len, size_t len) \
+    { return mat_stats<T>(MC##SFX(m), false, true, len, MR_OUT_STATS, sizeof(*out), out, out_len); }       \
+    int32_t bdsp_hip_mat_complex_statistics_split##SFX(const MB* m, ComplexStatistics##SFX* out, size_t out_len, size_t len) \
+    { return mat_stats<T>(MC##SFX(m), true, true, len, MR_OUT_STATS, sizeof(*out), out, out_len); }        \
+    int32_t bdsp_hip_mat_real_statistics_split_prec##SFX(const MB* m, Statistics64* out, size_t out_len, size_t len) \
+    { return mat_stats<T>(MC##SFX(m), false, true, len, MR_OUT_STATS_PREC, sizeof(*out), out, out_len); }  \
+    int32_t bdsp_hip_mat_complex_statistics_split_prec##SFX(const MB* m, ComplexStatistics64* out, size_t out_len, size_t len) \
+    { return mat_stats<T>(MC##SFX(m), true, true, len, MR_OUT_STATS_PREC, sizeof(*out), out, out_len); }   \
+    int32_t bdsp_hip_mat_real_sum##SFX(const MB* m, T* out, size_t len)                                     \
+    { return mat_stats<T>(MC##SFX(m), false, false, 1, MR_OUT_SUM, sizeof(*out), out, len); }              \
+    int32_t bdsp_hip_mat_real_sum_sq##SFX(const MB* m, T* out, size_t len)                                  \
+    { return mat_stats<T>(MC##SFX(m), false, false, 1, MR_OUT_SUM_SQ, sizeof(*out), out, len); }           \
+    int32_t bdsp_hip_mat_real_sum_prec##SFX(const MB* m, double* out, size_t len)                           \
+    { return mat_stats<T>(MC##SFX(m), false, false, 1, MR_OUT_SUM_PREC, sizeof(*out), out, len); }         \
+    int32_t bdsp_hip_mat_real_sum_sq_prec##SFX(const MB* m, double* out, size_t len)                        \
+    { return mat_stats<T>(MC##SFX(m), false, false, 1, MR_OUT_SUM_SQ_PREC, sizeof(*out), out, len); }      \
+    int32_t bdsp_hip_mat_complex_sum##SFX(const MB* m, bdsp_complex##SFX* out, size_t len)                  \
+    { return mat_stats<T>(MC##SFX(m), true, false, 1, MR_OUT_SUM, sizeof(*out), out, len); }               \
+    int32_t bdsp_hip_mat_complex_sum_sq##SFX(const MB* m, bdsp_complex##SFX* out, size_t len)               \
+    { return mat_stats<T>(MC##SFX(m), true, false, 1, MR_OUT_SUM_SQ, sizeof(*out), out, len); }            \
+    int32_t bdsp_hip_mat_complex_sum_prec##SFX(const MB* m, bdsp_complex64* out, size_t len)                \
+    { return mat_stats<T>(MC##SFX(m), true, false, 1, MR_OUT_SUM_PREC, sizeof(*out), out, len); }          \
+    int32_t bdsp_hip_mat_complex_sum_sq_prec##SFX(const MB* m, bdsp_complex64* out, size_t len)             \
+    { return mat_stats<T>(MC##SFX(m), true, false, 1, MR_OUT_SUM_SQ_PREC, sizeof(*out), out, len); }       \
+    int32_t bdsp_hip_mat_real_dot_product##SFX(const MB* m, const MB* factor, T* out, size_t len)           \
+    { return mat_dot_mat<T>(MC##SFX(m), MC##SFX(factor), false, MR_OUT_SUM, sizeof(*out), out, len); }     \
+    int32_t bdsp_hip_mat_complex_dot_product##SFX(const MB* m, const MB* factor, bdsp_complex##SFX* out, size_t len) \
+    { return mat_dot_mat<T>(MC##SFX(m), MC##SFX(factor), true, MR_OUT_SUM, sizeof(*out), out, len); }      \
+    int32_t bdsp_hip_mat_real_dot_product_prec##SFX(const MB* m, const MB* factor, double* out, size_t len)  \
+    { return mat_dot_mat<T>(MC##SFX(m), MC##SFX(factor), false, MR_OUT_SUM_PREC, sizeof(*out), out, len); } \
+    int32_t bdsp_hip_mat_complex_dot_product_prec##SFX(const MB* m, const MB* factor, bdsp_complex64* out, size_t len) \
+    { return mat_dot_mat<T>(MC##SFX(m), MC##SFX(factor), true, MR_OUT_SUM_PREC, sizeof(*out), out, len); } \
+    int32_t bdsp_hip_mat_real_dot_product_vector##SFX(const MB* m, const VB* factor, T* out, size_t len)    \
+    { return mat_dot_vec<T>(MC##SFX(m), H<T>(factor), false, MR_OUT_SUM, sizeof(*out), out, len); }        \
+    int32_t bdsp_hip_mat_complex_dot_product_vector##SFX(const MB* m, const VB* factor, bdsp_complex##SFX* out, size_t len) \
+    { return mat_dot_vec<T>(MC##SFX(m), H<T>(factor), true, MR_OUT_SUM, sizeof(*out), out, len); }         \
+    int32_t bdsp_hip_mat_real_dot_product_vector_prec##SFX(const MB* m, const VB* factor, double* out, size_t len) \
+    { return mat_dot_vec<T>(MC##SFX(m), H<T>(factor), false, MR_OUT_SUM_PREC, sizeof(*out), out, len); }   \
+    int32_t bdsp_hip_mat_complex_dot_product_vector_prec##SFX(const MB* m, const VB* factor, bdsp_complex64* out, size_t len) \
+    { return mat_dot_vec<T>(MC##SFX(m), H<T>(factor), true, MR_OUT_SUM_PREC, sizeof(*out), out, len); }
+
+BDSP_MAT_STATS(32, float, MatBuf32, VecBuf32)
+BDSP_MAT_STATS(64, double, MatBuf64, VecBuf64)
+#undef BDSP_MAT_STATS
 
 // ---------------------------------------------------------------------------------------------- B3
 int bdsp_hip_dev_fft(int elem, void* data, void* scratch, size_t points, size_t batch, unsigned flags,

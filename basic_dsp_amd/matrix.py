@@ -181,3 +181,78 @@ class DspMat:
 
     def multiply_frequency_response(self, function, ratio, rolloff=0.0):
         return self._call("multiply_frequency_response", int(function), rolloff, ratio)
+
+    # ------------------------------------------------------------------ per-row statistics, sums, dot products
+    # One batched device pass each (matrix/src/general/statistics.rs, mod.rs); results per row as numpy columns.
+    _STAT_KEYS = ("sum", "count", "average", "rms", "min", "min_index", "max", "max_index")
+
+    def _out_dtypes(self, prec):
+        """(result struct, scalar dtype, complex dtype) of this matrix's precision, or double with prec"""
+        if prec or self._sfx == "64":
+            st = _lib.ComplexStatistics64 if self.is_complex() else _lib.Statistics64
+            return st, np.float64, np.complex128
+        st = _lib.ComplexStatistics32 if self.is_complex() else _lib.Statistics32
+        return st, np.float32, np.complex64
+
+    def _stats(self, split, length, prec):
+        cplx = self.is_complex()
+        st, _, cdt = self._out_dtypes(prec)
+        n = self.rows() * (length if split else 1)
+        arr = np.zeros(n, dtype=np.dtype(st))  # the #[repr(C)] layout, filled by one copy
+        name = ("complex" if cplx else "real") + "_statistics" + ("_split" if split else "") + ("_prec" if prec else "")
+        args = (arr.ctypes.data_as(C.POINTER(st)), n) + ((int(length),) if split else ())
+        code = self._call(name, *args)
+        cols = {}
+        for k in self._STAT_KEYS:
+            col = arr[k]
+            if k in ("count", "min_index", "max_index"):
+                cols[k] = col.astype(np.int64)
+            elif cplx:
+                z = np.empty(n, dtype=cdt)
+                z.real, z.imag = col["re"], col["im"]
+                cols[k] = z
+            else:
+                cols[k] = col.copy()
+        return code, cols
+
+    def statistics(self, prec=False):
+        """StatisticsOps / PreciseStatisticsOps per row: dict of arrays of length rows (keys of DspVec.statistics)."""
+        return self._stats(False, 1, prec)[1]
+
+    def statistics_split(self, length, prec=False):
+        """(code, dict of arrays shaped [rows, length]); element j of a row goes to bucket j % length."""
+        code, cols = self._stats(True, length, prec)
+        if code not in (0, -1):
+            return code, {}
+        return code, {k: v.reshape(self.rows(), int(length)) for k, v in cols.items()}
+
+    def _value_out(self, prec):
+        """one (complex) value per row: the array and the pointer the C ABI takes"""
+        _, rdt, cdt = self._out_dtypes(prec)
+        out = np.zeros(self.rows(), dtype=cdt if self.is_complex() else rdt)
+        ct = {np.float32: C.c_float, np.float64: C.c_double, np.complex64: _lib.Complex32,
+              np.complex128: _lib.Complex64}[out.dtype.type]
+        return out, out.ctypes.data_as(C.POINTER(ct))
+
+    def _sums(self, which, prec):
+        cplx = self.is_complex()
+        out, ptr = self._value_out(prec)
+        name = ("complex" if cplx else "real") + which + ("_prec" if prec else "")
+        self._call(name, ptr, out.size)
+        return out
+
+    def sum(self, prec=False):
+        return self._sums("_sum", prec)
+
+    def sum_sq(self, prec=False):
+        return self._sums("_sum_sq", prec)
+
+    def dot_product(self, other, prec=False):
+        """(code, array of one value per row): row r with row r of a DspMat, or every row with one DspVec.
+        Codes as DspVec.dot_product (4 / 3 / 2), 7 for unequal row counts, -1 poisoned."""
+        cplx = self.is_complex()
+        out, ptr = self._value_out(prec)
+        name = ("complex" if cplx else "real") + "_dot_product" + ("_vector" if isinstance(other, DspVec) else "") + \
+            ("_prec" if prec else "")
+        code = self._call(name, other._h, ptr, out.size)
+        return code, out

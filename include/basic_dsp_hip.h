@@ -693,6 +693,37 @@ int32_t bdsp_hip_mat_convolve_signal_mat32(MatBuf32 *m, const VecBuf32 *const *i
 int32_t bdsp_hip_mat_interpolatef32(MatBuf32 *m, int32_t impulse_response, float rolloff,
                                     float interpolation_factor, float delay, size_t conv_len);
 int32_t bdsp_hip_mat_multiply_frequency_response32(MatBuf32 *m, int32_t frequency_response, float rolloff, float ratio);
+/* Per-row statistics, sums and dot products: one result per row in out[0 .. rows) (split: out[r*len + b], bucket b of
+ * row r), one batched device pass.  `len` (split: `out_len`) must equal rows (rows * len), else 7; split len > 16 gives 7,
+ * len 0 gives 0 and writes nothing.  Indices are within the row.  real_* walks every scalar of a row, complex_* its
+ * pairs, as the vector facade.  Dot products: 4 (real_* on a complex matrix), 3 (complex_* on a real one), 2 (complex
+ * operand not complex or in another domain), 7 for matrices with unequal row counts (stricter than the reference's
+ * zip, as bdsp_hip_mat_add), per-row count min(row length, operand length), complex products not conjugated.
+ * -1 for a poisoned matrix, results written as the vector path writes them. */
+int32_t bdsp_hip_mat_real_statistics32(const MatBuf32 *m, Statistics32 *out, size_t len);                 /* matrix/src/general/statistics.rs:4-19 */
+int32_t bdsp_hip_mat_complex_statistics32(const MatBuf32 *m, ComplexStatistics32 *out, size_t len);
+int32_t bdsp_hip_mat_real_statistics_prec32(const MatBuf32 *m, Statistics64 *out, size_t len);             /* :240-255 */
+int32_t bdsp_hip_mat_complex_statistics_prec32(const MatBuf32 *m, ComplexStatistics64 *out, size_t len);
+int32_t bdsp_hip_mat_real_statistics_split32(const MatBuf32 *m, Statistics32 *out, size_t out_len, size_t len);       /* :21-36 */
+int32_t bdsp_hip_mat_complex_statistics_split32(const MatBuf32 *m, ComplexStatistics32 *out, size_t out_len, size_t len);
+int32_t bdsp_hip_mat_real_statistics_split_prec32(const MatBuf32 *m, Statistics64 *out, size_t out_len, size_t len);   /* :257-272 */
+int32_t bdsp_hip_mat_complex_statistics_split_prec32(const MatBuf32 *m, ComplexStatistics64 *out, size_t out_len, size_t len);
+int32_t bdsp_hip_mat_real_sum32(const MatBuf32 *m, float *out, size_t len);                                     /* :140-163 */
+int32_t bdsp_hip_mat_real_sum_sq32(const MatBuf32 *m, float *out, size_t len);
+int32_t bdsp_hip_mat_complex_sum32(const MatBuf32 *m, bdsp_complex32 *out, size_t len);
+int32_t bdsp_hip_mat_complex_sum_sq32(const MatBuf32 *m, bdsp_complex32 *out, size_t len);
+int32_t bdsp_hip_mat_real_sum_prec32(const MatBuf32 *m, double *out, size_t len);                           /* :376-400 */
+int32_t bdsp_hip_mat_real_sum_sq_prec32(const MatBuf32 *m, double *out, size_t len);
+int32_t bdsp_hip_mat_complex_sum_prec32(const MatBuf32 *m, bdsp_complex64 *out, size_t len);
+int32_t bdsp_hip_mat_complex_sum_sq_prec32(const MatBuf32 *m, bdsp_complex64 *out, size_t len);
+int32_t bdsp_hip_mat_real_dot_product32(const MatBuf32 *m, const MatBuf32 *factor, float *out, size_t len);   /* matrix/src/general/mod.rs:9-25 */
+int32_t bdsp_hip_mat_complex_dot_product32(const MatBuf32 *m, const MatBuf32 *factor, bdsp_complex32 *out, size_t len);
+int32_t bdsp_hip_mat_real_dot_product_prec32(const MatBuf32 *m, const MatBuf32 *factor, double *out, size_t len);    /* :153-169 */
+int32_t bdsp_hip_mat_complex_dot_product_prec32(const MatBuf32 *m, const MatBuf32 *factor, bdsp_complex64 *out, size_t len);
+int32_t bdsp_hip_mat_real_dot_product_vector32(const MatBuf32 *m, const VecBuf32 *factor, float *out, size_t len);     /* :81-97 */
+int32_t bdsp_hip_mat_complex_dot_product_vector32(const MatBuf32 *m, const VecBuf32 *factor, bdsp_complex32 *out, size_t len);
+int32_t bdsp_hip_mat_real_dot_product_vector_prec32(const MatBuf32 *m, const VecBuf32 *factor, double *out, size_t len);   /* :225-241 */
+int32_t bdsp_hip_mat_complex_dot_product_vector_prec32(const MatBuf32 *m, const VecBuf32 *factor, bdsp_complex64 *out, size_t len);
 
 MatBuf64 *bdsp_hip_mat_new64(int32_t is_complex, int32_t domain, size_t rows, size_t row_len, double delta); /* row_len in scalars; zero filled */
 void bdsp_hip_mat_delete64(MatBuf64 *m);
@@ -742,6 +773,31 @@ int32_t bdsp_hip_mat_convolve_signal_mat64(MatBuf64 *m, const VecBuf64 *const *i
 int32_t bdsp_hip_mat_interpolatef64(MatBuf64 *m, int32_t impulse_response, double rolloff,
                                     double interpolation_factor, double delay, size_t conv_len);
 int32_t bdsp_hip_mat_multiply_frequency_response64(MatBuf64 *m, int32_t frequency_response, double rolloff, double ratio);
+/* per-row statistics, sums and dot products: as the f32 set above */
+int32_t bdsp_hip_mat_real_statistics64(const MatBuf64 *m, Statistics64 *out, size_t len);                 /* matrix/src/general/statistics.rs:4-19 */
+int32_t bdsp_hip_mat_complex_statistics64(const MatBuf64 *m, ComplexStatistics64 *out, size_t len);
+int32_t bdsp_hip_mat_real_statistics_prec64(const MatBuf64 *m, Statistics64 *out, size_t len);             /* :240-255 */
+int32_t bdsp_hip_mat_complex_statistics_prec64(const MatBuf64 *m, ComplexStatistics64 *out, size_t len);
+int32_t bdsp_hip_mat_real_statistics_split64(const MatBuf64 *m, Statistics64 *out, size_t out_len, size_t len);       /* :21-36 */
+int32_t bdsp_hip_mat_complex_statistics_split64(const MatBuf64 *m, ComplexStatistics64 *out, size_t out_len, size_t len);
+int32_t bdsp_hip_mat_real_statistics_split_prec64(const MatBuf64 *m, Statistics64 *out, size_t out_len, size_t len);   /* :257-272 */
+int32_t bdsp_hip_mat_complex_statistics_split_prec64(const MatBuf64 *m, ComplexStatistics64 *out, size_t out_len, size_t len);
+int32_t bdsp_hip_mat_real_sum64(const MatBuf64 *m, double *out, size_t len);                                     /* :140-163 */
+int32_t bdsp_hip_mat_real_sum_sq64(const MatBuf64 *m, double *out, size_t len);
+int32_t bdsp_hip_mat_complex_sum64(const MatBuf64 *m, bdsp_complex64 *out, size_t len);
+int32_t bdsp_hip_mat_complex_sum_sq64(const MatBuf64 *m, bdsp_complex64 *out, size_t len);
+int32_t bdsp_hip_mat_real_sum_prec64(const MatBuf64 *m, double *out, size_t len);                           /* :376-400 */
+int32_t bdsp_hip_mat_real_sum_sq_prec64(const MatBuf64 *m, double *out, size_t len);
+int32_t bdsp_hip_mat_complex_sum_prec64(const MatBuf64 *m, bdsp_complex64 *out, size_t len);
+int32_t bdsp_hip_mat_complex_sum_sq_prec64(const MatBuf64 *m, bdsp_complex64 *out, size_t len);
+int32_t bdsp_hip_mat_real_dot_product64(const MatBuf64 *m, const MatBuf64 *factor, double *out, size_t len);   /* matrix/src/general/mod.rs:9-25 */
+int32_t bdsp_hip_mat_complex_dot_product64(const MatBuf64 *m, const MatBuf64 *factor, bdsp_complex64 *out, size_t len);
+int32_t bdsp_hip_mat_real_dot_product_prec64(const MatBuf64 *m, const MatBuf64 *factor, double *out, size_t len);    /* :153-169 */
+int32_t bdsp_hip_mat_complex_dot_product_prec64(const MatBuf64 *m, const MatBuf64 *factor, bdsp_complex64 *out, size_t len);
+int32_t bdsp_hip_mat_real_dot_product_vector64(const MatBuf64 *m, const VecBuf64 *factor, double *out, size_t len);     /* :81-97 */
+int32_t bdsp_hip_mat_complex_dot_product_vector64(const MatBuf64 *m, const VecBuf64 *factor, bdsp_complex64 *out, size_t len);
+int32_t bdsp_hip_mat_real_dot_product_vector_prec64(const MatBuf64 *m, const VecBuf64 *factor, double *out, size_t len);   /* :225-241 */
+int32_t bdsp_hip_mat_complex_dot_product_vector_prec64(const MatBuf64 *m, const VecBuf64 *factor, bdsp_complex64 *out, size_t len);
 
 /* ==========================================================================================
  * B3 -- kernels on caller-owned DEVICE memory.  `stream` is a hipStream_t passed as void*
