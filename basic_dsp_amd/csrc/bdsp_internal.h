@@ -61,7 +61,8 @@ __device__ __forceinline__ void nt_store(C* p, C v)
     __builtin_nontemporal_store(vec2{v.x, v.y}, reinterpret_cast<vec2*>(p));
 }
 
-// Streaming load (experiment, LAB builds with -DBDSP_FFT_NTLOAD: a pass's input is dead once read)
+// Streaming load of one complex value: the first pass of an f64 transform reads its input, dead once read, this way
+// (k_fft_pass NTL)
 template <typename C>
 __device__ __forceinline__ C nt_load(const C* p)
 {
@@ -72,16 +73,6 @@ __device__ __forceinline__ C nt_load(const C* p)
 }
 
 int num_cus();
-
-// Experiment switches (tools/plan_probe.py, tools/chunk_probe.py, A/B runs) exist only in the LAB build of the library
-// (`make -C basic_dsp_amd/csrc lab` -> lib/libbasic_dsp_hip_lab.so, -DBDSP_LAB); the product reads no environment
-// variable and carries no kernel that only such a switch could reach.
-#ifdef BDSP_LAB
-inline const char* lab_env(const char* name) { return getenv(name); }
-#else
-inline const char* lab_env(const char*) { return nullptr; }
-#endif
-inline bool lab_flag(const char* name) { return lab_env(name) != nullptr; }
 
 struct WsBlock { // RAII workspace
     void* p = nullptr;

@@ -60,21 +60,20 @@ int fft_two_buffers(T* a, T* b, size_t points, size_t batch, bool inverse, unsig
         io.out = a;
         // a -> b -> b from 2^19 points on: the last pass reads and writes the same index set per workgroup, so it may run in
         // place, and the working set of that pass halves.  *Measured* on valid data, input AND scratch cold / input in the
-        // caches (tools/plan_probe.py, profiles/r05_plan_probe_valid.txt; rounds 2-4 had this for ONE 2^21-point f32 vector
+        // caches (profiles/r05_plan_probe_valid.txt; rounds 2-4 had this for ONE 2^21-point f32 vector
         // only, chosen in loops that ran on inf / NaN): f32 2^19 15.2 -> 13.9 / 12.0 -> 10.8 us, 2^20 16.9 -> 16.6 / 15.8 -> 15.2,
         // 2^21 29.6 -> 24.3 / 25.1 -> 19.8, 2^22 43.3 -> 42.8 / 33.4 -> 32.9; f64 2^19 20.4 -> 17.5 / 18.5 -> 16.1, 2^20 22.6 -> 22.2 / =,
         // 2^21 37.3 -> 36.6 / =, 2^22 69.6 -> 66.9 / 46.4 -> 47.2, 16 x 2^20 f64 218.8 -> 214.0 / 213.5 -> 203.2, 64 x 2^20 f32 equal.
         // Below 2^19 nothing moves (2^14 ... 2^18: +-0.2 us) except batches, which LOSE (256 x 2^16 f32: 83.5 -> 97-100 us with the
         // input in the caches), and 2^24's third pass in place measured 135 against 128 us (below).
-        static const bool force_inplace = lab_flag("BDSP_FFT_LAST_INPLACE"), no_inplace = lab_flag("BDSP_FFT_NO_LAST_INPLACE");
-        if (!reshaping && !no_inplace && (force_inplace || points >= (size_t(1) << 19))) {
+        if (!reshaping && points >= (size_t(1) << 19)) {
             io.out = b;
             *in_b = true;
             return fft_pow2<T>(io, b, nullptr, batch, inverse, s);
         }
         // (Rounds 2-4 sent a large batch through in Infinity-Cache-sized chunks of vectors -- 64 x 1M-point f32: "402 us in one
         // piece, 372 us in chunks of 16", measured in a loop that fed the transform its own output, i.e. on inf / NaN.  On
-        // valid data, cold and cache-resident (tools/plan_probe.py, profiles/r05_plan_probe_valid.txt): one piece 421 / 420 us,
+        // valid data, cold and cache-resident (profiles/r05_plan_probe_valid.txt): one piece 421 / 420 us,
         // chunks of 16 423 / 438, of 32 441 / 439, of 8 508 / 500; with a magnitude output 402 / 409 against 404 / 402; 32 x 1M
         // f64 404 / 397 against 426 / 422.  The chunks are gone.)
         return fft_pow2<T>(io, b, nullptr, batch, inverse, s);
@@ -180,8 +179,7 @@ int fft_any_len(T* a, T* b, size_t n, size_t batch, bool inverse, unsigned flags
                 int window_id, T window_alpha, bool* in_b, hipStream_t s)
 {
     *in_b = false;
-    static const bool no_mixed = lab_flag("BDSP_FFT_NO_MIXED_RADIX");
-    if (!no_mixed && mr_supported<T>(n) && (batch <= 65535 || mr_resident<T>(n))) {
+    if (mr_supported<T>(n) && (batch <= 65535 || mr_resident<T>(n))) {
         // 2,3,5,7-smooth lengths: mixed-radix Stockham (mixed_radix.hip).  The four-step form goes a -> b -> a; the
         // workgroup-resident form runs in place unless the output has another shape than the input.
         const bool reshaping = (flags & (FFT_IN_REAL | BDSP_FFT_MAGNITUDE | FFT_OUT_REAL)) != 0;
@@ -234,13 +232,13 @@ int check_device()
 // Small host slices travel through a per-thread PINNED staging buffer (hipHostMalloc, grown geometrically; signals of at
 // most B1_STAGE_MAX bytes), and where the kernels allow it they are not copied by the GPU at all: the first kernel reads the
 // staging buffer over PCIe and the last one writes it.  *Measured* (tools/b1_crossover.py, profiles/r06_b1_crossover.txt; wall
-// time of one call, f32; "stage k" = LAB build with BDSP_B1_STAGE=k):
+// time of one call, f32; "stage k" = every call staged in mode k):
 //   * stage 0, pageable copies (rounds 1-5): a floor of 34-47 us from 4096 to 16384 points -- launch, two copy packets and the
 //     completion wait, not the pinning of the caller's pages;
 //   * stage 1, pinned copies: 0-5 us better on a complex vector, 15-40 us on real / f64 ones up to 1 MiB, and WORSE from
 //     2 MiB on, where the runtime pins the caller's pages itself and two host memcpys cost more than that (2^18 points
 //     122 -> 272 us);
-//   * stage 2, kernels read the stage, the result is copied down: another 2-7 us;
+//   * stage 2, kernels read the stage, the result is copied down: another 2-7 us (not kept: stage 3 beats it);
 //   * stage 3, no copy packet at all, is what moves the floor: fft 4096 points 36 -> 20 us, 8192 41 -> 26, 16384 47 -> 29,
 //     65536 81 -> 58, 131072 (1 MiB) 147 -> 137; convolve_vector 5001 x 5 taps 45 -> 29, 16384 x 1024 56 -> 39, 131072 x 1024
 //     166 -> 122; real data 131072 x 5 taps 96 -> 71.  Above 1 MiB every staged form loses to the pageable path.
@@ -286,8 +284,6 @@ std::atomic<size_t> g_b1_policy[B1_POLICY_KEYS] = {
 
 int b1_stage_mode(size_t bytes, bool zero_copy_ok)
 {
-    static const char* force = lab_env("BDSP_B1_STAGE");
-    if (force) return bytes <= (size_t(64) << 20) ? atoi(force) : 0;
     if (bytes > B1_STAGE_MAX) return 0;
     return zero_copy_ok ? 3 : 1;
 }
@@ -310,27 +306,22 @@ int b1_fft(int is_complex, T* signal, size_t len, int inverse)
     int mode = b1_stage_mode(bytes, pow2 || smooth);
     char* stage = mode ? t_b1stage.get(bytes) : nullptr;
     if (!stage) mode = 0;
-    if (mode >= 2 && !(pow2 || smooth)) mode = 1;
     WsBlock a, b;
-    if (mode >= 2) {
-        // the first pass reads the pinned stage over PCIe; with mode 3 the last pass writes it: stage -> a [-> b] -> stage
+    if (mode == 3) {
+        // the first pass reads the pinned stage over PCIe and the last pass writes it: stage -> a [-> b] -> stage
         memcpy(stage, signal, bytes);
         if (smooth) {
-            if (mode == 2 || !mr_resident<T>(points)) BDSP_TRY(a.alloc(bytes, s));
-            T* dst = mode == 3 ? (T*)stage : a.as<T>();
-            if (mode == 2 && !mr_resident<T>(points)) BDSP_TRY(b.alloc(bytes, s));
-            BDSP_TRY(mr_fft<T>((const T*)stage, dst, mode == 3 ? a.as<T>() : b.as<T>(), points, 1, inverse != 0, 0, (T)1, -1, (T)0, s));
-            if (mode == 2) BDSP_HIP_TRY(hipMemcpyAsync(stage, a.p, bytes, hipMemcpyDeviceToHost, s));
+            if (!mr_resident<T>(points)) BDSP_TRY(a.alloc(bytes, s));
+            BDSP_TRY(mr_fft<T>((const T*)stage, (T*)stage, a.as<T>(), points, 1, inverse != 0, 0, (T)1, -1, (T)0, s));
         } else {
             if (trips >= 2 || points > 4096) BDSP_TRY(a.alloc(bytes, s)); // (8192 f32: one kernel, but the two-pass plan is its fallback)
-            if (trips >= 3 || mode == 2) BDSP_TRY(b.alloc(bytes, s));
+            if (trips >= 3) BDSP_TRY(b.alloc(bytes, s));
             FftIo<T> io{};
             io.n = points; io.flags = 0; io.in_scale = (T)1; io.window_id = -1; io.window_alpha = (T)0;
             io.in_stride = points; io.out_stride = points;
             io.in = stage;
-            io.out = mode == 3 ? (void*)stage : b.p;
+            io.out = stage;
             BDSP_TRY(fft_pow2<T>(io, a.as<T>(), trips >= 3 ? b.as<T>() : nullptr, 1, inverse != 0, s));
-            if (mode == 2) BDSP_HIP_TRY(hipMemcpyAsync(stage, b.p, bytes, hipMemcpyDeviceToHost, s));
         }
         BDSP_HIP_TRY(hipStreamSynchronize(s));
         memcpy(signal, stage, bytes);
@@ -434,15 +425,8 @@ int conv_real_dev(const T* in, T* out, size_t points, const T* taps, size_t ntap
     }
     if (!(ntaps >= 1 && ntaps <= FUSED_MAX_TAPS && ntaps <= points))
         return convolve_direct<T>(in, out, points, batch, taps, ntaps, false, s);
-    static const bool real_prep = lab_flag("BDSP_CONV_REAL_PREP"); // (LAB: spectrum in its own launch, round 5)
-    if (!real_prep) // one launch: the block kernel reads the real taps and transforms them itself
-        return conv_run_blocks<T>(in, out, points, batch, taps, ntaps, -(long long)(ntaps / 2), 0, 0, nullptr, s, true, true);
-    WsBlock hc, hsb;
-    BDSP_TRY(hc.alloc(sizeof(T) * 2 * ntaps, s));
-    BDSP_TRY(hsb.alloc(sizeof(T) * 2 * conv_fft_len(ntaps), s));
-    BDSP_TRY(rg_zero_interleave<T>(taps, hc.as<T>(), ntaps, 1, 2, s));
-    BDSP_TRY(conv_prepare_spectrum<T>(hc.as<T>(), ntaps, nullptr, hsb.as<T>(), s));
-    return conv_run_blocks<T>(in, out, points, batch, hsb.as<T>(), ntaps, -(long long)(ntaps / 2), 0, 0, nullptr, s, true);
+    // one launch: the block kernel reads the real taps and transforms them itself
+    return conv_run_blocks<T>(in, out, points, batch, taps, ntaps, -(long long)(ntaps / 2), 0, 0, nullptr, s, true, true);
 }
 
 // gpu_convolve_vector on a long complex vector: the PCIe transfers dominate (128 MiB each way for 16M f32 points
@@ -613,8 +597,7 @@ int b1_convolve(int is_complex, const T* src, size_t src_len, T* dst, size_t dst
     int c = check_device();
     if (c != BDSP_OK) return c;
     hipStream_t s = lib_stream();
-    static const bool no_pipeline = lab_flag("BDSP_B1_NO_PIPELINE");
-    if (is_complex && !no_pipeline && points >= (size_t(1) << 20) && ntaps <= FUSED_MAX_TAPS && points < (size_t(1) << 31)) {
+    if (is_complex && points >= (size_t(1) << 20) && ntaps <= FUSED_MAX_TAPS && points < (size_t(1) << 31)) {
         BDSP_TRY(b1_convolve_pipelined<T>(src, dst, points, imp, ntaps));
         if (range_start) *range_start = 0;
         if (range_end) *range_end = src_len;
@@ -625,12 +608,13 @@ int b1_convolve(int is_complex, const T* src, size_t src_len, T* dst, size_t dst
     const size_t ioff = (sbytes + 255) & ~(size_t)255;
     const bool block_kernel = ntaps <= FUSED_MAX_TAPS; // the fused kernel reads every input point ~1.3 times: fit for PCIe reads
     int mode = b1_stage_mode(sbytes, block_kernel); // (the limit counts the signal; the taps ride along)
-    if (mode >= 2 && !block_kernel) mode = 1;
     char* stage = mode ? t_b1stage.get(mode == 3 ? 2 * ioff + ibytes + 256 : ioff + ibytes) : nullptr;
     if (!stage) mode = 0;
     WsBlock dx, dy;
-    if (mode < 2) BDSP_TRY(dx.alloc(ioff + ibytes, s));
-    if (mode < 3) BDSP_TRY(dy.alloc(sbytes, s));
+    if (mode < 3) {
+        BDSP_TRY(dx.alloc(ioff + ibytes, s));
+        BDSP_TRY(dy.alloc(sbytes, s));
+    }
     if (mode) {
         memcpy(stage, src, sbytes);
         memcpy(stage + ioff, imp, ibytes);
@@ -640,7 +624,7 @@ int b1_convolve(int is_complex, const T* src, size_t src_len, T* dst, size_t dst
         BDSP_HIP_TRY(hipMemcpyAsync(dx.p, src, sbytes, hipMemcpyHostToDevice, s));
         BDSP_HIP_TRY(hipMemcpyAsync((char*)dx.p + ioff, imp, ibytes, hipMemcpyHostToDevice, s));
     }
-    const T* din = mode >= 2 ? (const T*)stage : dx.as<T>();
+    const T* din = mode == 3 ? (const T*)stage : dx.as<T>();
     const T* dtaps = (const T*)((const char*)din + ioff);
     T* dout = mode == 3 ? (T*)(stage + ioff + ((ibytes + 255) & ~(size_t)255)) : dy.as<T>();
     if (is_complex) BDSP_TRY(conv_complex_dev<T>(din, dout, points, 1, dtaps, ntaps, s));

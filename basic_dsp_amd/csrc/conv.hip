@@ -63,13 +63,10 @@ size_t conv_fft_len(size_t) { return CONV_L; }
 //     complex transform pair as real and imaginary part (convolution with a real filter is
 //     real-linear, so they come out separated) -- half the butterflies and 8 B of traffic per sample
 //     instead of complexify -> convolve -> project (40 B per sample).
-// Experiment switch: -DBDSP_CONV_HL2=1 re-reads H from L2 per block and builds for 4 workgroups per CU
-// (128 VGPRs).  Measured 96 us against 80 us with H in registers at 3 per CU -- kept for reference.
-#ifndef BDSP_CONV_HL2
-#define BDSP_CONV_HL2 0
-#endif
+// H stays in registers: re-reading it from L2 per block at 4 workgroups per CU (128 VGPRs) measured 96 us against
+// 80 us with H in registers at 3 per CU.
 template <typename T, bool FAST, bool REAL>
-__global__ __launch_bounds__(256, sizeof(T) == 4 ? (BDSP_CONV_HL2 ? 4 : 3) : 2) void k_overlap_save(
+__global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void k_overlap_save(
     const void* __restrict__ x_, void* __restrict__ y_, const cpx<T>* __restrict__ hs,
     const cpx<T>* __restrict__ wtab, unsigned n, int m_taps, long long in_off, long long out_off,
     unsigned blocks_per_vec, unsigned out_limit, int store_all)
@@ -90,12 +87,11 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? (BDSP_CONV_HL2 ? 4 : 3) : 2) 
     const T hscale = (T)1 / (T)L; // the inverse transform below is unnormalised
     auto tw = [&](int mm) { return wtab[mm]; };
 
-    constexpr bool HREG = !BDSP_CONV_HL2;
     // stage 3 in FMA form (fft_core.h dft16_tw, round 3): f32 holds its eight twiddle values, f64 two (w^2, w) and
     // derives the rest -- the six-value split it replaces cost nine complex multiplies per transform and 8 more registers
     // (the f64 REAL instantiation spilled 28 bytes per lane)
     constexpr bool F32 = sizeof(T) == 4;
-    cpx<T> tw3f[F32 ? 8 : 2], hreg[HREG ? 16 : 1];
+    cpx<T> tw3f[F32 ? 8 : 2], hreg[16];
     cpx<T>* tw2l = lds + F::LDS_ELEMS;
     if constexpr (F32) F::template load_twiddles16_fma<256>(tw3f, t, tw);
     else { tw3f[0] = wtab[2 * t]; tw3f[1] = wtab[t]; }
@@ -108,15 +104,11 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? (BDSP_CONV_HL2 ? 4 : 3) : 2) 
             dft16_tw<DIR>(&v[0], tl);
         }
     };
-    {
-        if constexpr (HREG) {
-            if (!(store_all & 2)) {
+    if (!(store_all & 2)) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    cpx<T> hv = hs[ut + 256u * r];
-                    hreg[r] = cpx<T>{hv.x * hscale, hv.y * hscale};
-                }
-            }
+        for (int r = 0; r < 16; ++r) {
+            cpx<T> hv = hs[ut + 256u * r];
+            hreg[r] = cpx<T>{hv.x * hscale, hv.y * hscale};
         }
     }
     // stage-2 twiddles (16 distinct rows of 15) in LDS for both builds
@@ -126,34 +118,32 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? (BDSP_CONV_HL2 ? 4 : 3) : 2) 
     }
     __syncthreads();
     const cpx<T>* tw2p = tw2l + (t & 15) * 17;
-    if constexpr (HREG) {
-        // store_all bit 1: `hs` holds the TAPS, not their spectrum -- every workgroup transforms the zero-padded taps
-        // itself (half a block of extra work per workgroup, in parallel) and keeps the result where the block loop wants
-        // it: X[t + 256 r] in register r.  Saves the separate 7 us spectrum launch and its round trip through memory.
-        if (store_all & 2) {
-            cpx<T> hv[16];
+    // store_all bit 1: `hs` holds the TAPS, not their spectrum -- every workgroup transforms the zero-padded taps
+    // itself (half a block of extra work per workgroup, in parallel) and keeps the result where the block loop wants
+    // it: X[t + 256 r] in register r.  Saves the separate 7 us spectrum launch and its round trip through memory.
+    if (store_all & 2) {
+        cpx<T> hv[16];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const unsigned i = ut + 256u * r;
-                // bit 2: the taps are REAL scalars (real signal, real filter)
-                if (store_all & 4) hv[r] = i < (unsigned)m_taps ? cpx<T>{reinterpret_cast<const T*>(hs)[i], (T)0} : cpx<T>{(T)0, (T)0};
-                else hv[r] = i < (unsigned)m_taps ? hs[i] : cpx<T>{(T)0, (T)0};
-            }
-            auto twh = [&](int mm) { return wtab[mm]; };
-            F::template compute<16, 1, -1>(hv, t, twh);
-            F::scatter_a(hv, t, lds);
-            __syncthreads();
-            F::gather_a(hv, t, lds);
-            F::template compute_pre<16, 16, -1>(hv, tw2p);
-            __syncthreads();
-            F::scatter_b(hv, t, lds);
-            __syncthreads();
-            F::gather_b(hv, t, lds);
-            stage3(hv, std::integral_constant<int, -1>{});
-#pragma unroll
-            for (int r = 0; r < 16; ++r) hreg[r] = cpx<T>{hv[r].x * hscale, hv[r].y * hscale};
-            __syncthreads();
+        for (int r = 0; r < 16; ++r) {
+            const unsigned i = ut + 256u * r;
+            // bit 2: the taps are REAL scalars (real signal, real filter)
+            if (store_all & 4) hv[r] = i < (unsigned)m_taps ? cpx<T>{reinterpret_cast<const T*>(hs)[i], (T)0} : cpx<T>{(T)0, (T)0};
+            else hv[r] = i < (unsigned)m_taps ? hs[i] : cpx<T>{(T)0, (T)0};
         }
+        auto twh = [&](int mm) { return wtab[mm]; };
+        F::template compute<16, 1, -1>(hv, t, twh);
+        F::scatter_a(hv, t, lds);
+        __syncthreads();
+        F::gather_a(hv, t, lds);
+        F::template compute_pre<16, 16, -1>(hv, tw2p);
+        __syncthreads();
+        F::scatter_b(hv, t, lds);
+        __syncthreads();
+        F::gather_b(hv, t, lds);
+        stage3(hv, std::integral_constant<int, -1>{});
+#pragma unroll
+        for (int r = 0; r < 16; ++r) hreg[r] = cpx<T>{hv[r].x * hscale, hv[r].y * hscale};
+        __syncthreads();
     }
     const size_t vec = blockIdx.y;
     // per-vector bases; a REAL vector has n real samples (half the bytes of n complex ones)
@@ -222,17 +212,8 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? (BDSP_CONV_HL2 ? 4 : 3) : 2) 
     const unsigned G = gridDim.x;
     // one block: transform the 16 register-resident inputs and store the valid outputs
     auto process = [&](cpx<T> (&v)[16], unsigned b) {
-        const cpx<T>* hp = hs + t;
-        const cpx<T>* wt = wtab;
-        if constexpr (!HREG) {
-            // keep the spectrum / twiddle loads inside the loop (hoisted they would pin > 150 VGPRs)
-            asm volatile("" : "+v"(hp));
-            asm volatile("" : "+s"(wt));
-        }
-        auto twl = [&](int mm) { return wt[mm]; };
-
         // ---- forward FFT_L
-        F::template compute<16, 1, -1>(v, t, twl);
+        F::template compute<16, 1, -1>(v, t, tw);
         __syncthreads(); // previous block's last gather is done
         F::scatter_a(v, t, lds);
         __syncthreads();
@@ -246,16 +227,10 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? (BDSP_CONV_HL2 ? 4 : 3) : 2) 
 
         // ---- spectrum product
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            if constexpr (HREG) v[r] = cmul(v[r], hreg[r]);
-            else {
-                cpx<T> hv = hp[256 * r];
-                v[r] = cmul(v[r], cpx<T>{hv.x * hscale, hv.y * hscale});
-            }
-        }
+        for (int r = 0; r < 16; ++r) v[r] = cmul(v[r], hreg[r]);
 
         // ---- inverse FFT_L
-        F::template compute<16, 1, 1>(v, t, twl);
+        F::template compute<16, 1, 1>(v, t, tw);
         __syncthreads();
         F::scatter_a(v, t, lds);
         __syncthreads();
@@ -402,9 +377,7 @@ int conv_run_blocks(const T* in, T* out, size_t points, size_t batch, const T* h
 {
     constexpr int L = CONV_L;
     // real data with real taps handed in as taps: the second-generation kernel on pairs of real blocks
-    // (LAB, BDSP_CONV_REAL_PREP: also on a prepared spectrum, so that the workgroups need not transform the taps themselves)
-    static const bool real_prep = lab_flag("BDSP_CONV_REAL_PREP");
-    if (real_data && (hs_is_taps || real_prep) && !last_block_out && nblocks_limit == 0 && out_off == 0 && in_off == -(long long)(taps / 2) &&
+    if (real_data && hs_is_taps && !last_block_out && nblocks_limit == 0 && out_off == 0 && in_off == -(long long)(taps / 2) &&
         taps >= 1 && taps - 1 <= 3 * (size_t)L / 4 && conv_v2_applies(points, taps))
         return conv_v2_run<T>(in, out, points, batch, hs, taps, 0, 0, hs_is_taps, s, true);
     // complex data: the second-generation kernel (conv_v2.hip) whenever the call is a run of whole blocks
@@ -439,7 +412,7 @@ int conv_run_blocks(const T* in, T* out, size_t points, size_t batch, const T* h
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // persistent-ish grid: enough workgroups to fill every CU at the occupancy LDS/VGPRs allow,
     // each walking blocks with a grid stride so the register-resident twiddles are loaded once
-    int per_cu = sizeof(T) == 4 ? (BDSP_CONV_HL2 ? 4 : 3) : 2;
+    int per_cu = sizeof(T) == 4 ? 3 : 2;
     long long want = (long long)num_cus() * per_cu;
     long long gx = (want + (long long)batch - 1) / (long long)batch;
     if (gx > per_vec) gx = per_vec;
@@ -469,8 +442,7 @@ int convolve_overlap_save(const T* in, T* out, size_t points, size_t batch, cons
                           T* last_block_out, const T* h_freq_dev, hipStream_t s)
 {
     // with the taps in hand the block kernel transforms them itself (one launch for the whole convolution)
-    static const bool no_fused_taps = lab_flag("BDSP_CONV_NO_FUSED_TAPS");
-    if (!BDSP_CONV_HL2 && taps_dev && !h_freq_dev && !last_block_out && !no_fused_taps)
+    if (taps_dev && !h_freq_dev && !last_block_out)
         return conv_run_blocks<T>(in, out, points, batch, taps_dev, taps, in_off, out_off, nblocks_limit, nullptr, s,
                                   false, true);
     WsBlock hsb;

@@ -36,7 +36,6 @@
 //     that is already the busiest; not built.
 #include "bdsp_internal.h"
 #include <atomic>
-#include <cstdlib>
 #include <type_traits>
 
 namespace bdsp {
@@ -57,12 +56,7 @@ struct ConvV2Args {
     unsigned na, nbb;        // interior blocks (all vectors together) given to dispatch groups 0 and 1
     int hs_is_taps;
     unsigned groups;         // dispatch groups = workgroups per CU: 3 (f32), 2 (f64)
-    unsigned stagger_us;     // LAB experiment (BDSP_CONV_STAGGER_US): dispatch groups after the first start this much later
 };
-
-// (ablations: a value the compiler must treat as defined / as used, without an instruction)
-template <typename C> static __device__ __forceinline__ void abl_def(C& v) { asm volatile("" : "=v"(v.x), "=v"(v.y)); }
-template <typename C> static __device__ __forceinline__ void abl_use(const C& v) { asm volatile("" : : "v"(v.x), "v"(v.y)); }
 
 static __device__ __forceinline__ unsigned xcd_contiguous(unsigned bid, unsigned g)
 {
@@ -76,13 +70,10 @@ static __device__ __forceinline__ unsigned xcd_contiguous(unsigned bid, unsigned
 // REAL: the vector holds n REAL samples and the taps are real: the real blocks 2p and 2p+1 travel through the complex
 // transform pair as real and imaginary part (convolution with a real filter is real-linear, so they come out
 // separated).  "Block" then means such a PAIR; x, y and hs are read as arrays of T.
-// ABL (LAB build only, BDSP_CONV_ABL=<bits>, R0 = 4): timing-only ablations of the interior loop -- 1 no global loads,
-// 2 no global stores, 8 no transform (3 = arithmetic + exchanges alone, 8 = the memory skeleton alone); the output is
-// garbage.  They put a measured bound next to the f64 and real-data kernels' roofline fractions.
 // NTS: the interior blocks' results are STREAMED (non-temporal stores) -- for results the 256 MB Infinity Cache cannot hold
 // anyway (round 5, conv_v2_streams_result below; round 3 measured the compile-time form on the headline step: +8 us, its
 // 128 MB result is read back from the cache by the transform that follows).
-template <typename T, int R0, bool BATCHED, bool REAL = false, int ABL = 0, bool NTS = false>
+template <typename T, int R0, bool BATCHED, bool REAL = false, bool NTS = false>
 __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void k_overlap_save_v2(ConvV2Args<T> a)
 {
     constexpr int L = L2;
@@ -267,12 +258,6 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void k_overlap_save_v2
     const unsigned ni = a.nb_hi - a.nb_lo, total = ni * a.batch, gs = G / a.groups;
     const unsigned grp = blockIdx.x / gs;
     if (grp >= a.groups) return;
-#ifdef BDSP_LAB
-    if (a.stagger_us && grp > 0) { // (bounded: s_memrealtime counts 100 MHz ticks)
-        const unsigned long long t0 = wall_clock64(), lim = (unsigned long long)a.stagger_us * 100ull * grp;
-        while (wall_clock64() - t0 < lim) __builtin_amdgcn_s_sleep(32);
-    }
-#endif
     const unsigned lo = grp == 0 ? 0u : (grp == 1 ? a.na : a.na + a.nbb);
     const unsigned hi = grp == 0 ? a.na : ((grp == 1 && a.groups == 3) ? a.na + a.nbb : total);
     // (Round 3, measured and NOT adopted: RUNS of consecutive blocks per workgroup.  Block b + 1's first R0 rows are block
@@ -290,222 +275,42 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void k_overlap_save_v2
             const T* x0 = reinterpret_cast<const T*>(a.x) + ((size_t)vec * a.n + ((long long)(2 * b) * V + in_off));
             T* y0 = reinterpret_cast<T*>(a.y) + ((size_t)vec * a.n + ((long long)(2 * b) * V - OV));
             C32 v[16];
-            if constexpr (ABL & 1) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) abl_def(v[r]);
-            } else {
+            for (int r = 0; r < 16; ++r) v[r] = C32{x0[ut + 256u * r], x0[V + ut + 256u * r]};
+            transform(v);
 #pragma unroll
-                for (int r = 0; r < 16; ++r) v[r] = C32{x0[ut + 256u * r], x0[V + ut + 256u * r]};
-            }
-            if constexpr (!(ABL & 8)) transform(v);
-            if constexpr (ABL & 2) {
-#pragma unroll
-                for (int r = R0; r < 16; ++r) abl_use(v[r]);
-            } else {
-#pragma unroll
-                for (int r = R0; r < 16; ++r) {
-                    y0[ut + 256u * r] = v[r].x;
-                    y0[V + ut + 256u * r] = v[r].y;
-                }
+            for (int r = R0; r < 16; ++r) {
+                y0[ut + 256u * r] = v[r].x;
+                y0[V + ut + 256u * r] = v[r].y;
             }
             continue;
         }
         const C32* xb = a.x + ((size_t)vec * a.n + ((long long)b * V + in_off));
         C32* yb = a.y + ((size_t)vec * a.n + ((long long)b * V - OV));
         C32 v[16];
-        if constexpr (ABL & 1) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) abl_def(v[r]);
-        } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-#if defined(BDSP_LAB) && defined(BDSP_CONV_NTL)
-                v[r] = nt_load(&xb[ut + 256u * r]); // (A/B build, round 5: the input is dead once read)
-#else
-                v[r] = xb[ut + 256u * r];
-#endif
-            }
-        }
-        if constexpr (!(ABL & 8)) transform(v);
-        if constexpr (ABL & 2) {
-#pragma unroll
-            for (int r = R0; r < 16; ++r) abl_use(v[r]);
-            continue;
-        }
+        for (int r = 0; r < 16; ++r) v[r] = xb[ut + 256u * r];
+        transform(v);
 #pragma unroll
         for (int r = R0; r < 16; ++r) {
             // (non-temporal stores measured 7 us slower on the FFT that follows: the result would leave the caches;
             // non-temporal loads of x made no difference)
-            // (round 3, -DBDSP_CONV_NT in the lab build: streaming stores pay only when the result exceeds the cache --
-            // 16M f64 points (256 MB) 129 -> 123 us, 64 x 1M f32 (512 MB) 232 -> 228 -- and cost the headline step 8 us)
+            // (round 3: streaming stores pay only when the result exceeds the cache -- 16M f64 points (256 MB)
+            // 129 -> 123 us, 64 x 1M f32 (512 MB) 232 -> 228 -- and cost the headline step 8 us)
             if constexpr (NTS) nt_store(&yb[ut + 256u * r], v[r]);
             else yb[ut + 256u * r] = v[r];
         }
     }
 }
 
-#ifdef BDSP_LAB
-// ------------------------------------------------------------------------------------------------------------------
-// LAB experiment, round 5 (BDSP_CONV_V3=1; complex f64, 770 ... 1025 taps: the block step of the product's R0 = 4): the third candidate of VERDICT r04's item 4 --
-// the same block, 512 threads x EIGHT points per thread, 4096 = 8 x 8 x 8 x 8.  Half the registers per wave (v and H are
-// 32 VGPRs each instead of 64: a 128-register budget), so a CU holds two 512-thread workgroups = FOUR waves per SIMD where
-// the product kernel has two, at the price of a fourth stage and a third LDS exchange per transform (12 barriers per
-// block instead of 8).  Rows are 512 points: R0 = ceil((M - 1) / 512) = 2 discarded rows for 1024 taps, V = 3072 as in the
-// product.  Stage-2 / stage-3 twiddles (four values per thread: dft8_tw) from LDS tables of 8 x 4 and 64 x 4 entries,
-// stage 4 from two held values {w^2, w} (w^4 by squaring, w W8 by a constant).  128 VGPRs, no scratch, four waves per SIMD.
-// *Measured* (tools/conv_probe.py: correct on its first run, 6.3e-16 rel-L2 from the product kernel's result): 145.5-150.2 us
-// against 120.5-123.1 -- twice the waves buy nothing, the fourth stage and the third exchange cost 20 %.  Not adopted.
-template <int R0, bool NTS>
-__global__ __launch_bounds__(512, 4) void k_overlap_save_v3(ConvV2Args<double> a)
-{
-    using T = double;
-    constexpr int L = L2, NTH = 512;
-    constexpr unsigned V = L - 512 * R0, OV = 512 * R0;
-    using C64 = cpx<T>;
-    using F = WgFft<T, L, NTH>;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    C64* lds = reinterpret_cast<C64*>(smem_raw);
-    const int t = threadIdx.x;
-    const unsigned ut = t;
-    const T hscale = (T)1 / (T)L;
-    auto tww = [&](int mm) { return a.wtab[mm]; };
-    C64* tw2l = lds + F::LDS_ELEMS;       // [8][4]
-    C64* tw3l = tw2l + 8 * 4;             // [64][4]
-    if (t < 32) {
-        const int k = t >> 2, j = t & 3, e = k * (L / 64);
-        tw2l[t] = a.wtab[j == 0 ? 4 * e : j == 1 ? 2 * e : j == 2 ? e : e + L / 8];
-    }
-    if (t < 256) {
-        const int k = t >> 2, j = t & 3, e = k * (L / 512);
-        tw3l[t] = a.wtab[j == 0 ? 4 * e : j == 1 ? 2 * e : j == 2 ? e : e + L / 8];
-    }
-    const C64 w4q[2] = {a.wtab[(2 * t) & (L - 1)], a.wtab[t]}; // stage 4 (NS = 512): e = t -> {w^2, w}
-    __syncthreads();
-    const C64* tw2p = tw2l + (t & 7) * 4;
-    const C64* tw3p = tw3l + (t & 63) * 4;
-    auto stage_tab = [&](C64 (&v)[8], const C64* tp, auto D) {
-        const C64 tl[4] = {tp[0], tp[1], tp[2], tp[3]};
-        dft8_tw<decltype(D)::value>(&v[0], tl);
-    };
-    auto stage4 = [&](C64 (&v)[8], auto D) {
-        const T h = (T)0.70710678118654752440;
-        const C64 w2 = w4q[0], w1 = w4q[1];
-        const C64 tl[4] = {C64{(w2.x - w2.y) * (w2.x + w2.y), (T)2 * w2.x * w2.y}, w2, w1, C64{(w1.x + w1.y) * h, (w1.y - w1.x) * h}};
-        dft8_tw<decltype(D)::value>(&v[0], tl);
-    };
-    auto xform = [&](C64 (&v)[8], auto D) {
-        constexpr int DIR = decltype(D)::value;
-        F::template compute<8, 1, DIR>(v, t, tww);
-        __syncthreads(); // the previous transform's last gather is done
-        F::template scatter<8, 1>(v, t, lds);
-        __syncthreads();
-        F::template gather<8>(v, t, lds);
-        stage_tab(v, tw2p, D);
-        __syncthreads();
-        F::template scatter<8, 8>(v, t, lds);
-        __syncthreads();
-        F::template gather<8>(v, t, lds);
-        stage_tab(v, tw3p, D);
-        __syncthreads();
-        F::template scatter<8, 64>(v, t, lds);
-        __syncthreads();
-        F::template gather<8>(v, t, lds);
-        stage4(v, D);
-    };
-    // ---- the filter spectrum, delayed by d samples, x 1/L: H'[t + 512 r] in register r
-    C64 hreg[8];
-    const unsigned d = OV - (a.taps - 1);
-    {
-        C64 hv[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const unsigned i = ut + 512u * r;
-            hv[r] = (i >= d && i - d < a.taps) ? a.hs[i - d] : C64{(T)0, (T)0};
-        }
-        xform(hv, std::integral_constant<int, -1>{});
-#pragma unroll
-        for (int r = 0; r < 8; ++r) hreg[r] = C64{hv[r].x * hscale, hv[r].y * hscale};
-    }
-    auto transform = [&](C64 (&v)[8]) {
-        xform(v, std::integral_constant<int, -1>{});
-#pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = cmul(v[r], hreg[r]);
-        xform(v, std::integral_constant<int, 1>{});
-    };
-    const long long in_off = -(long long)(a.taps / 2);
-    const unsigned G = gridDim.x;
-    // ---- blocks that wrap around the ends of the vector: general code, taken first
-    {
-        const unsigned nw = (a.nb_lo - a.b_first) + (a.b_end - a.nb_hi), total_w = nw * a.batch;
-        for (unsigned w = blockIdx.x; w < total_w; w += G) {
-            const unsigned vec = w / nw, k = w % nw;
-            const unsigned b = k < a.nb_lo - a.b_first ? a.b_first + k : a.nb_hi + (k - (a.nb_lo - a.b_first));
-            const C64* xv = a.x + (size_t)vec * a.n;
-            C64* yv = a.y + (size_t)vec * a.n;
-            long long sb = ((long long)b * V + in_off) % (long long)a.n;
-            if (sb < 0) sb += a.n;
-            C64 v[8];
-#pragma unroll
-            for (int r = 0; r < 8; ++r) v[r] = xv[((unsigned long long)sb + ut + 512u * r) % a.n];
-            transform(v);
-            const long long obase = (long long)b * V - OV;
-            const long long room = (long long)a.n - obase;
-            const unsigned lim = room <= 0 ? 0u : (room > L ? (unsigned)L : (unsigned)room);
-            C64* yb = yv + obase;
-#pragma unroll
-            for (int r = R0; r < 8; ++r) {
-                const unsigned np = ut + 512u * r;
-                if (np < lim) yb[np] = v[r];
-            }
-        }
-    }
-    // ---- interior blocks: two dispatch groups with skewed shares, as in the product kernel
-    const unsigned ni = a.nb_hi - a.nb_lo, total = ni * a.batch, gs = G / a.groups;
-    const unsigned grp = blockIdx.x / gs;
-    if (grp >= a.groups) return;
-    const unsigned lo = grp == 0 ? 0u : a.na;
-    const unsigned hi = grp == 0 ? a.na : total;
-    const unsigned w2 = xcd_contiguous(blockIdx.x - grp * gs, gs);
-    for (unsigned id = lo + w2; id < hi; id += gs) {
-        const unsigned vec = id / ni, b = a.nb_lo + id % ni;
-        const C64* xb = a.x + ((size_t)vec * a.n + ((long long)b * V + in_off));
-        C64* yb = a.y + ((size_t)vec * a.n + ((long long)b * V - OV));
-        C64 v[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = xb[ut + 512u * r];
-        transform(v);
-#pragma unroll
-        for (int r = R0; r < 8; ++r) {
-            if constexpr (NTS) nt_store(&yb[ut + 512u * r], v[r]);
-            else yb[ut + 512u * r] = v[r];
-        }
-    }
-}
-#endif // BDSP_LAB
+// (512 threads x 8 points per f64 block, k_overlap_save_v3: measured 20 % slower, round 5 -- docs/HISTORY.md)
 
 template <typename T, int R0>
 static int launch_v2(const ConvV2Args<T>& a, unsigned grid, size_t lds, hipStream_t s, bool real, bool nts)
 {
-#ifdef BDSP_LAB
-    if constexpr (R0 == 4) {
-        if (const char* e = lab_env("BDSP_CONV_ABL")) {
-            const int abl = atoi(e);
-#define BDSP_ABL(N)                                                                                                     \
-    if (abl == N) {                                                                                                     \
-        auto kern = real ? k_overlap_save_v2<T, R0, true, true, N> : k_overlap_save_v2<T, R0, true, false, N>;          \
-        if (lds > 64 * 1024) BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a);                                                     \
-        BDSP_LAUNCH_CHECK();                                                                                            \
-        return BDSP_OK;                                                                                                 \
-    }
-            BDSP_ABL(3) BDSP_ABL(8)
-#undef BDSP_ABL
-        }
-    }
-#endif
     // streamed results: complex data only, through the batched instantiation (it serves single vectors too)
     if (!real && nts) {
-        auto kern = k_overlap_save_v2<T, R0, true, false, 0, true>;
+        auto kern = k_overlap_save_v2<T, R0, true, false, true>;
         if (lds > 64 * 1024) BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a);
         BDSP_LAUNCH_CHECK();
@@ -529,7 +334,7 @@ static int launch_v2(const ConvV2Args<T>& a, unsigned grid, size_t lds, hipStrea
 }
 
 // results above this size are streamed: see k_overlap_save_v2 NTS (set from the measurements of round 5)
-// *Measured* (tools/conv_probe.py, profiles/r05_conv_probe.txt): 16M complex f64 points (256 MB in, 256 MB out), twelve interleaved
+// *Measured* (round 5, profiles/r05_conv_probe.txt): 16M complex f64 points (256 MB in, 256 MB out), twelve interleaved
 // runs each way in two processes: 121.5 / 123.0 -> 118.8 / 120.3 us (-2.2 %; single runs move by +-5 % on one box); 64 x 1M f32
 // (512 MB) 225 -> 222 us for the kernel and 629 -> 632 for convolve -> fft, so f32 batches are left alone; the headline's 128 MB
 // result must NOT be streamed (step 181 -> 192 us: the transform reads it from the cache).
@@ -559,8 +364,7 @@ void conv_v2_set_shares(int first_pct, int second_pct)
 
 bool conv_v2_applies(size_t points, size_t taps)
 {
-    static const bool off = lab_flag("BDSP_CONV_V1");
-    return !off && taps >= 1 && taps - 1 <= 3 * (size_t)L2 / 4 && points >= 1 && points < (size_t(1) << 31);
+    return taps >= 1 && taps - 1 <= 3 * (size_t)L2 / 4 && points >= 1 && points < (size_t(1) << 31);
 }
 #endif
 
@@ -589,17 +393,12 @@ int conv_v2_run(const T* in, T* out, size_t points, size_t batch, const T* hs, s
         set_last_error("convolve_overlap_save: too many blocks");
         return BDSP_ERR_UNSUPPORTED;
     }
-    constexpr unsigned GROUPS_MAX = sizeof(T) == 4 ? 3 : 2; // what the kernel's register budget allows per CU
-    // (LAB: fewer workgroups per CU for the real-data kernel, whose 16M-sample job is 3.6 pairs per workgroup at three)
-    static const unsigned lab_groups = [] { const char* e = lab_env("BDSP_CONV_GROUPS"); return e ? (unsigned)atoi(e) : 0u; }();
-    const unsigned GROUPS = (lab_groups >= 2 && lab_groups <= GROUPS_MAX) ? lab_groups : GROUPS_MAX;
+    constexpr unsigned GROUPS = sizeof(T) == 4 ? 3 : 2; // what the kernel's register budget allows per CU
     ConvV2Args<T> a{};
     a.groups = GROUPS;
-    a.stagger_us = [] { const char* e = lab_env("BDSP_CONV_STAGGER_US"); return e ? (unsigned)atoi(e) : 0u; }();
     // A complex result larger than the Infinity Cache can hold until its reader comes is streamed past the caches
-    // (DESIGN.md 4.3, round 5); LAB: BDSP_CONV_NTS=0 / 1 forces the choice
-    bool nts = !real && conv_v2_streams_result<T>(points, batch);
-    if (const char* e = lab_env("BDSP_CONV_NTS")) nts = !real && atoi(e) != 0;
+    // 
+    const bool nts = !real && conv_v2_streams_result<T>(points, batch);
     a.x = reinterpret_cast<const cpx<T>*>(in);
     a.y = reinterpret_cast<cpx<T>*>(out);
     a.hs = reinterpret_cast<const cpx<T>*>(hs);
@@ -637,19 +436,6 @@ int conv_v2_run(const T* in, T* out, size_t points, size_t batch, const T* hs, s
     a.na = (unsigned)na;
     a.nbb = (unsigned)nbb;
     const size_t lds = (size_t)(sizeof(T) == 4 ? WgFft<T, L2, 256>::LDS_ELEMS3 : WgFft<T, L2, 256>::LDS_ELEMS + 16 * 17) * sizeof(cpx<T>);
-#ifdef BDSP_LAB
-    if constexpr (sizeof(T) == 8) {
-        if (lab_flag("BDSP_CONV_V3") && !real && r0 == 4 && GROUPS == 2) {
-            using F3 = WgFft<double, L2, 512>;
-            const size_t lds3 = (size_t)(F3::LDS_ELEMS + 8 * 4 + 64 * 4) * sizeof(cpx<double>);
-            auto kern = nts ? k_overlap_save_v3<2, true> : k_overlap_save_v3<2, false>;
-            BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds3, s, a);
-            BDSP_LAUNCH_CHECK();
-            return BDSP_OK;
-        }
-    }
-#endif
     switch (r0) {
 #define BDSP_R0(N) case N: return launch_v2<T, N>(a, grid, lds, s, real, nts);
         BDSP_R0(1) BDSP_R0(2) BDSP_R0(3) BDSP_R0(4) BDSP_R0(5) BDSP_R0(6)

@@ -16,7 +16,6 @@
 // Window, 1/N scale, fft_shift / ifft_shift and magnitude are fused into the first / last pass
 // (FftIo), so fft()/windowed_fft()/ifft() never take an extra trip through HBM
 // (reference: time_to_freq.rs:158-175, freq_to_time.rs:160-177 run them as separate passes).
-#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
@@ -39,7 +38,7 @@ namespace bdsp {
 
 template <typename T>
 int launch_pass_opts_rp(int rp, int w, const FftIo<T>& io, const cpx<T>* src, cpx<T>* dst, size_t n, size_t nsg, size_t batch,
-                        bool inverse, bool first, bool last, hipStream_t s, int tl, int aux);
+                        bool inverse, bool first, bool last, hipStream_t s);
 template <typename T>
 int launch_wg_gen(int n, const FftIo<T>& io, size_t batch, bool inverse, hipStream_t s);
 
@@ -132,9 +131,6 @@ __host__ __device__ constexpr int pass_wgs_per_cu(size_t lds_bytes, int threads)
 template <typename T, int RP, int W, bool GEN>
 constexpr bool pass_split_exchange()
 {
-#if defined(BDSP_LAB) && defined(BDSP_FFT_NO_SPLIT)
-    return false; // (A/B build: tools/plan_matrix.sh, round 5 -- the whole-complex exchange of round 2, one workgroup per CU)
-#endif
     return !GEN && sizeof(T) == 8 && (size_t)W * col_stride(RP, W) * sizeof(cpx<T>) > 80 * 1024;
 }
 template <typename T, int RP, int W, bool GEN>
@@ -519,24 +515,16 @@ __device__ __forceinline__ void pass_window16(const FftIo<T>& io, size_t i0, siz
     }
 }
 
-// TL (round 4): the TILED intermediate of a two-pass plan.  The first pass's output layout is nobody's business but the
-// second pass's, which reads, per tile, W2 adjacent columns of it: W2 x 8 (16) bytes per row -- 32-64-byte runs wherever
-// the columns are long (1024 / 2048 points).  With mid'[k1 / W2][j][k1 % W2] (k1 = the first pass's output index = the
-// second pass's column, j = the first pass's column = the second pass's row) a second-pass tile is ONE contiguous
-// RP2 x W2 block, and the first pass still stores whole lines (W1 x W2 adjacent values per k1 group, lanes along the
-// columns).  TL = 1: first pass, tiled store (aux = log2 W2); TL = 2: last pass, tiled load.  The natural-order input of
-// the first pass and output of the last keep their W-wide runs.
 // WIN: -1 = the window id is read at run time (and is Hamming / Hann where the tile uses the split exchange); 0 / 2: the
 // split-exchange tiles' instantiations for the triangular and the Blackman-Harris window (pass_window16 FIXED).
 // NTL (round 5): the FIRST pass reads its input -- dead once read -- with non-temporal loads.  f64 only, and only where the
 // tile's runs are whole 128-byte lines (pass_ntl_candidate): see launch_pass for the measurements.
-template <typename T, int RP, int W, int DIR, bool ROWMAP, bool GEN, bool SIMPLE = false, int TL = 0, int WIN = -1, bool NTL = false>
+template <typename T, int RP, int W, int DIR, bool ROWMAP, bool GEN, bool SIMPLE = false, int WIN = -1, bool NTL = false>
 __global__ __launch_bounds__(W * (RP / 16), (pass_min_waves<T, RP, W, GEN>())) void k_fft_pass(FftIo<T> io, const cpx<T>* src, // (src may equal dst: the in-place last pass)
                                                    cpx<T>* dst,
                                                    const cpx<T>* __restrict__ wtab, size_t n,
-                                                   size_t nsg, size_t tiles_per_vec, int last, int aux)
+                                                   size_t nsg, size_t tiles_per_vec, int last)
 {
-    static_assert(TL == 0 || (TL == 1 && ROWMAP) || (TL == 2 && !ROWMAP), "tiled store: first pass; tiled load: a later pass");
     constexpr int NT = RP / 16;
     constexpr int CS = col_stride(RP, W);
     using F = WgFft<T, RP, NT>;
@@ -585,20 +573,10 @@ __global__ __launch_bounds__(W * (RP / 16), (pass_min_waves<T, RP, W, GEN>())) v
             const T* inr = reinterpret_cast<const T*>(io.in) + vec * io.in_stride + j;
 #pragma unroll
             for (int r = 0; r < 16; ++r) v[r] = cpx<T>{inr[(size_t)(ti + (r ^ rx) * NT) * stride_in], (T)0};
-        } else if constexpr (TL == 2) {
-            const cpx<T>* in_t = src + vec * n + j0 * RP + c; // the tile's own RP x W block
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = in_t[(size_t)(ti + r * NT) * W];
         } else {
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                // (non-temporal loads, -DBDSP_FFT_NTLOAD in a LAB build: *measured* round 4, see DESIGN.md 4.2;
-                // -DBDSP_FFT_NTLOAD=2: in the FIRST pass only, whose input is dead once read -- round 5)
-#if defined(BDSP_LAB) && defined(BDSP_FFT_NTLOAD)
-                v[r] = (BDSP_FFT_NTLOAD != 2 || ROWMAP) ? nt_load(&in[(size_t)(ti + (r ^ rx) * NT) * stride_in]) : in[(size_t)(ti + (r ^ rx) * NT) * stride_in];
-#else
                 v[r] = NTL ? nt_load(&in[(size_t)(ti + (r ^ rx) * NT) * stride_in]) : in[(size_t)(ti + (r ^ rx) * NT) * stride_in];
-#endif
         }
         if (!SIMPLE && ROWMAP && io.in_scale != (T)1) {
 #pragma unroll
@@ -629,8 +607,8 @@ __global__ __launch_bounds__(W * (RP / 16), (pass_min_waves<T, RP, W, GEN>())) v
     }
 
     // ---- RP-point sub-FFT of every column
-    const int c2 = (ROWMAP && TL != 1) ? tid / NT : tid % W; // (a tiled store wants its lanes along the columns)
-    const int t2 = (ROWMAP && TL != 1) ? tid % NT : tid / W;
+    const int c2 = ROWMAP ? tid / NT : tid % W;
+    const int t2 = ROWMAP ? tid % NT : tid / W;
     LE* l1 = lds + (size_t)c * CS;
     LE* l2 = lds + (size_t)c2 * CS;
     if constexpr (SPLIT) {
@@ -670,19 +648,6 @@ __global__ __launch_bounds__(W * (RP / 16), (pass_min_waves<T, RP, W, GEN>())) v
     constexpr int RL = P::R3 > 1 ? P::R3 : P::R2;
     constexpr int NSL = RP / RL;
     const size_t jj = j0 + c2;
-    if constexpr (TL == 1) {
-        const int lw2 = aux;
-        const size_t ncols = n / RP;
-        cpx<T>* out = dst + vec * n;
-#pragma unroll
-        for (int b = 0; b < 16 / RL; ++b)
-#pragma unroll
-            for (int r = 0; r < RL; ++r) {
-                const unsigned k1 = (unsigned)F::template out_index<RL, NSL>(t2, b, r);
-                out[((((size_t)(k1 >> lw2)) * ncols + jj) << lw2) + (k1 & ((1u << lw2) - 1u))] = v[b * RL + r];
-            }
-        return;
-    }
     const size_t base = (jj / nsg) * nsg * RP + (jj % nsg);
     bool staged = false;
     if constexpr (GEN && !ROWMAP) {
@@ -731,145 +696,14 @@ __global__ __launch_bounds__(W * (RP / 16), (pass_min_waves<T, RP, W, GEN>())) v
         for (int b = 0; b < 16 / RL; ++b)
 #pragma unroll
             for (int r = 0; r < RL; ++r)
-                // (non-temporal stores here, -DBDSP_FFT_NT in the lab build: 16M f32 points 127 -> 181 us, C2 x 64 379 -> 427
-                // -- a pass's output is the next pass's input and the Infinity Cache holds it; 2^25 / 2^26 points and 16M f64,
-                // whose buffers exceed the cache: +-1 %; streaming only the LAST pass's result: no difference.  Not adopted.)
-#if defined(BDSP_LAB) && defined(BDSP_FFT_NT)
-                nt_store(&out[(size_t)F::template out_index<RL, NSL>(t2, b, r ^ sx) * nsg], v[b * RL + r]);
-#else
+                // (plain stores: non-temporal ones measured 16M f32 points 127 -> 181 us, C2 x 64 379 -> 427 -- a pass's output
+                // is the next pass's input and the Infinity Cache holds it; 2^25 / 2^26 points and 16M f64, whose buffers exceed
+                // the cache: +-1 %; streaming only the LAST pass's result: no difference.  DESIGN.md 4.2)
                 out[(size_t)F::template out_index<RL, NSL>(t2, b, r ^ sx) * nsg] = v[b * RL + r];
-#endif
     }
 }
 
-
-// ------------------------------------------------------------------------------ one 2^20-point vector (round 4, LAB only)
-// *Measured and NOT adopted* (profiles/r04_c2_tile_geometry.txt): correct for every output option (rel-L2 2.1e-7) and
-// 19.15 us against 17.2 us for the 1024 x 4 tiles -- the chain of a tile is memory latency, barriers and the launch
-// boundary, not instruction issue, so twice the waves at half the instructions each buy nothing and the doubled L2 -> CU
-// traffic costs.  Kept in the LAB build (BDSP_FFT_H512=1) so that the measurement can be repeated.
-// A single 1M-point f32 transform (BASELINE config C2) is two dependent launches of 256 tiles of 1024 x 4 points: ONE wave
-// per SIMD, nothing to hide the load -> butterflies -> store chain behind (9.1 + 8.0 us, of which ~1.7 us each are the
-// launch boundary; 17 MB in 9 us = 1.8 TB/s).  Here every 1024-point column transform is split in two by one
-// decimation-in-frequency step done in registers on load,
-//     X[2k]   = FFT_512(a + b)[k]                 a[n] = x[n], b[n] = x[n + 512]
-//     X[2k+1] = FFT_512((a - b) w_1024^n)[k]
-// and the halves go to DIFFERENT workgroups: 512 workgroups of 256 threads x 8 points (512 = 8 x 8 x 8: two LDS
-// exchanges as before), two per CU = two waves per SIMD, about half the instructions per wave; both workgroups of a tile
-// load all 1024 rows (the second read is an L2 hit).  Pass 1 writes half h of column j to mid[j 1024 + 512 h + k] (whole
-// contiguous runs; the parity interleave would be 8-byte pieces), so pass 2 finds output column 2k + h of pass 1 at
-// column position 512 h + k: its 4-wide tile takes positions {2t, 2t+1, 512 + 2t, 512 + 2t + 1} = the four ADJACENT true
-// columns 4t + {0, 2, 1, 3}.  Pass 2's outputs are rows 2 k' + h', 8 KB apart anyway.
-#ifdef BDSP_LAB
-template <int DIR, bool FIRST>
-__global__ __launch_bounds__(256) void k_fft_half512(FftIo<float> io, const cpx<float>* __restrict__ src, cpx<float>* __restrict__ dst,
-                                                      const cpx<float>* __restrict__ wtab /* exp(-2 pi i m / 1024) */)
-{
-    using T = float;
-    using C_ = cpx<T>;
-    constexpr int RP = 1024, H = 512, W = 4, NT = 64;
-    constexpr int CS = col_stride(H, W);
-    constexpr size_t N = (size_t)RP * RP;
-    using F = WgFft<T, H, NT>;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    C_* lds = reinterpret_cast<C_*>(smem_raw);
-    C_* ltw = lds + (size_t)W * CS; // the 1024-entry table
-    const int tid = threadIdx.x;
-    for (int i = tid; i < RP; i += 256) ltw[i] = wtab[i];
-    const unsigned tiles = RP / W; // 256
-    unsigned tile = blockIdx.x % tiles;
-    const unsigned h = blockIdx.x / tiles; // (blocks b and b + 256 sit on the same XCD: 256 % 8 == 0)
-    tile = (tile & 7) * (tiles >> 3) + (tile >> 3);
-    auto tw = [&](int m) { return ltw[2 * m]; }; // exp(-2 pi i m / 512)
-    const int c = tid % W, ti = tid / W;
-    C_ a[8], b[8];
-    unsigned kt = 0; // pass 2: the true column index of this lane's column
-    if (FIRST) {
-        const C_* in = src + (size_t)W * tile + c;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            a[r] = in[(size_t)(ti + 64 * r) * RP];
-            b[r] = in[(size_t)(ti + 64 * r + H) * RP];
-        }
-    } else {
-        const unsigned hh = c >> 1, kk = c & 1, pos = hh * H + 2 * tile + kk;
-        kt = 2 * (2 * tile + kk) + hh;
-        const C_* in = src + pos;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            a[r] = in[(size_t)(ti + 64 * r) * RP];
-            b[r] = in[(size_t)(ti + 64 * r + H) * RP];
-        }
-    }
-    __syncthreads(); // the table is in LDS
-    C_ v[8];
-    if (FIRST) {
-        if (h == 0) {
-#pragma unroll
-            for (int r = 0; r < 8; ++r) v[r] = cadd(a[r], b[r]);
-        } else {
-#pragma unroll
-            for (int r = 0; r < 8; ++r) v[r] = twmul<DIR>(csub(a[r], b[r]), ltw[ti + 64 * r]);
-        }
-    } else {
-        // inter-pass twiddle w_N^(n kt) on row n = ti + 64 r (+ 512 for b): a_r P_r and b_r P_r Q with P_r = bs d^r,
-        // bs = w_N^(ti kt), d = w_N^(64 kt), Q = w_N^(512 kt); the odd half's w_1024^n = w_N^(1024 n) joins bs and d
-        const unsigned e1 = h ? 1024u : 0u;
-        const C_ bs = unit_root<T>(((size_t)ti * (kt + e1)) & (N - 1), N);
-        const C_ d1 = unit_root<T>(((size_t)64 * (kt + e1)) & (N - 1), N);
-        const C_ q = unit_root<T>(((size_t)512 * kt) & (N - 1), N);
-        const C_ d2 = cmul(d1, d1), d4 = cmul(d2, d2);
-        C_ pw[8];
-        pw[0] = bs; pw[1] = cmul(bs, d1); pw[2] = cmul(bs, d2); pw[3] = cmul(pw[1], d2);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pw[4 + r] = cmul(pw[r], d4);
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const C_ tb = twmul<DIR>(b[r], q);
-            v[r] = twmul<DIR>(h ? csub(a[r], tb) : cadd(a[r], tb), pw[r]);
-        }
-    }
-    // ---- 512-point transform of every column: 8 x 8 x 8
-    F::template compute<8, 1, DIR>(v, ti, tw);
-    const int c2 = FIRST ? tid / NT : c, t2 = FIRST ? tid % NT : ti; // pass 1: lanes along rows for the contiguous store
-    C_* l1 = lds + (size_t)c * CS;
-    C_* l2 = lds + (size_t)c2 * CS;
-    F::template scatter<8, 1>(v, ti, l1);
-    __syncthreads();
-    F::template gather<8>(v, t2, l2);
-    F::template compute<8, 8, DIR>(v, t2, tw);
-    __syncthreads();
-    F::template scatter<8, 8>(v, t2, l2);
-    __syncthreads();
-    F::template gather<8>(v, t2, l2);
-    F::template compute<8, 64, DIR>(v, t2, tw);
-    // v[r] = Y_h[t2 + 64 r]
-    if (FIRST) {
-        C_* out = dst + ((size_t)W * tile + c2) * RP + (size_t)h * H + t2;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) out[64 * r] = v[r];
-    } else {
-        // true output row 2 k' + h; fft_shift = the row index's top bit flipped
-        const unsigned sx = (io.flags & BDSP_FFT_SHIFT_OUT) ? (unsigned)H : 0u;
-        if (io.flags & (BDSP_FFT_MAGNITUDE | FFT_OUT_REAL)) {
-            T* outr = reinterpret_cast<T*>(io.out) + kt;
-            const bool mag = (io.flags & BDSP_FFT_MAGNITUDE) != 0;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const unsigned row = (2u * (t2 + 64 * r) + h) ^ sx;
-                outr[(size_t)row * RP] = mag ? dev_hypot<T>(v[r].x, v[r].y) : v[r].x;
-            }
-        } else {
-            C_* out = dst + kt;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const unsigned row = (2u * (t2 + 64 * r) + h) ^ sx;
-                out[(size_t)row * RP] = v[r];
-            }
-        }
-    }
-}
-#endif // BDSP_LAB
+// (one 2^20-point f32 vector as two half-column launches, k_fft_half512: measured slower, round 4 -- docs/HISTORY.md A)
 
 // ------------------------------------------------------------------------------ launchers
 // plain complex in/out with the natural batch stride and no fused option?  The input side and the
@@ -946,15 +780,8 @@ static int launch_wg(const FftIo<T>& io, size_t batch, bool inverse, hipStream_t
     // round-2 figures came from loops on inf / NaN): f32 4096 x 4096 points 53.5 us cold / 46 hot against 61.3 / 49.7 for the
     // plain launch, 16384 x 4096 213 / 190 against 209-220 / 200-233; f64 LOSES at every size -- 16384 x 1024 points 107 / 94
     // against 97 / 89, x 2048 210 / 199 against 186 / 171, x 4096 439 / 426 against 387 / 374, 4096 x 4096 113 / 97 against
-    // 105 / 96 -- so its f64 instantiations exist in the LAB build only (BDSP_FFT_WGBATCH_F64).
-#ifdef BDSP_LAB
-    static const bool wgbatch_f64 = lab_flag("BDSP_FFT_WGBATCH_F64");
-    constexpr bool WGBATCH = N >= 1024;
-    const bool wgbatch_on = sizeof(T) == 4 || wgbatch_f64;
-#else
+    // 105 / 96 -- so it has no f64 instantiations.
     constexpr bool WGBATCH = N >= 1024 && sizeof(T) == 4;
-    const bool wgbatch_on = true;
-#endif
 #if BDSP_FFT_PART == 1
     if (gen) return launch_wg_gen<T>(N, io, batch, inverse, s); // the options unit
 #endif
@@ -970,8 +797,7 @@ static int launch_wg(const FftIo<T>& io, size_t batch, bool inverse, hipStream_t
             occ = o;
         }
         const size_t slots = (size_t)num_cus() * (size_t)occ;
-        static const bool no_wgbatch = lab_flag("BDSP_FFT_NO_WGBATCH");
-        if (wgbatch_on && !no_wgbatch && !gen && grid >= 4 * slots && !(io.flags & (BDSP_FFT_MAGNITUDE | FFT_OUT_REAL | FFT_IN_REAL))) {
+        if (!gen && grid >= 4 * slots && !(io.flags & (BDSP_FFT_MAGNITUDE | FFT_OUT_REAL | FFT_IN_REAL))) {
             if (inverse) {
                 BDSP_TRY(set_lds(k_fft_wg_batch<T, N, 1>, lds2));
                 hipLaunchKernelGGL((k_fft_wg_batch<T, N, 1>), dim3((unsigned)slots), dim3(256), lds2, s, io, wtab, batch);
@@ -1013,18 +839,6 @@ static int launch_tiny(const FftIo<T>& io, size_t batch, bool inverse, hipStream
     return BDSP_OK;
 }
 
-// column lengths whose pass kernels also exist with the tiled intermediate (TL): the long ones, whose tiles are narrow --
-// in the LAB build only (*measured*, round 4: not faster, see fft_pow2)
-template <int RP>
-constexpr bool pass_tiled_pair()
-{
-#ifdef BDSP_LAB
-    return RP >= 512;
-#else
-    return false;
-#endif
-}
-
 // first-pass tiles that read their (dead) input with non-temporal loads: f64, whole 128-byte lines per row (launch_pass)
 template <typename T, int RP, int W>
 constexpr bool pass_ntl_candidate()
@@ -1032,20 +846,16 @@ constexpr bool pass_ntl_candidate()
     return sizeof(T) == 8 && (size_t)W * sizeof(cpx<T>) >= 128;
 }
 
-// tiles the product's plans use as a FIRST pass only: their later-pass instantiations are not built (LAB: all are)
+// tiles the plans use as a FIRST pass only: their later-pass instantiations are not built
 template <int RP, int W>
 constexpr bool pass_first_only()
 {
-#ifdef BDSP_LAB
-    return false;
-#else
     return RP == 4096;
-#endif
 }
 
 template <typename T, int RP, int W>
 static int launch_pass(const FftIo<T>& io_in, const cpx<T>* src, cpx<T>* dst, size_t n, size_t nsg,
-                       size_t batch, bool inverse, bool first, bool last, hipStream_t s, int tl = 0, int aux = 0)
+                       size_t batch, bool inverse, bool first, bool last, hipStream_t s)
 {
     FftIo<T> io = io_in;
     const cpx<T>* const src0 = src;
@@ -1076,63 +886,57 @@ static int launch_pass(const FftIo<T>& io_in, const cpx<T>* src, cpx<T>* dst, si
     const bool simple = !gen && (rowmap ? ((io.flags & (FFT_IN_REAL | BDSP_FFT_SHIFT_IN)) == 0 && io.in_scale == (T)1 && io.window_id < 0)
                                         : (!last || (io.flags & (BDSP_FFT_SHIFT_OUT | BDSP_FFT_MAGNITUDE | FFT_OUT_REAL | FFT_WINDOW_OUT_DIV)) == 0));
 #if BDSP_FFT_PART == 1
-    if (!simple) return launch_pass_opts_rp<T>(RP, W, io_in, src0, dst0, n, nsg, batch, inverse, first, last, s, tl, aux); // the options unit
+    if (!simple) return launch_pass_opts_rp<T>(RP, W, io_in, src0, dst0, n, nsg, batch, inverse, first, last, s); // the options unit
 #endif
     // Non-temporal loads in the FIRST pass of an f64 transform whose tile reads whole 128-byte lines (W >= 8: the 3-pass plans'
-    // 256 x 16 / 128 x 32 tiles, the 1024 x 8 / 512 x 8 tiles of batches and of 2^18 points).  *Measured* (round 5, LAB build with
-    // -DBDSP_FFT_NTLOAD=2, cold / input in the caches, profiles/r05_plan_probe_valid.txt runs 4-5): 16 x 2^20 214 -> 185 / 205 -> 185 us,
+    // 256 x 16 / 128 x 32 tiles, the 1024 x 8 / 512 x 8 tiles of batches and of 2^18 points).  *Measured* (round 5, cold / input in
+    // the caches, profiles/r05_plan_probe_valid.txt runs 4-5): 16 x 2^20 214 -> 185 / 205 -> 185 us,
     // 4 x 2^20 61.6 -> 54.0 / =, 2^23 141 -> 133 / 130 -> 127, 2^24 327 -> 324 / 312 -> 304, 32 x 2^20 419 -> 417 / 404 -> 398, 256 x 2^16 and
     // 2^18 equal.  NOT where the tile reads half lines (2^21 / 2^22 f64 single vectors: cold 36.6 -> 33.7 / 67.2 -> 60.8 but with
     // the input in the caches 28.1 -> 32.5 / 46.1 -> 62.3 -- every half line becomes a fetch of its own), and not in f32, where it
     // is a wash or worse (2^23 -5 % cold, 2^24 -6 % cold / +1 % hot, 2^25 +6 %, 64 x 2^20 +8 %, 4096 x 2^14 +1 %).
     const bool ntl = pass_ntl_candidate<T, RP, W>() && first && rowmap && !gen && !(io.flags & FFT_IN_REAL);
-    // (tiled instantiations exist for the long columns only: pass_tiled_pair)
-    if (tl != 0 && (!pass_tiled_pair<RP>() || (tl == 1) != rowmap)) { set_last_error("tiled intermediate: unsupported pass"); return BDSP_ERR_UNSUPPORTED; }
-#define BDSP_PASS_K(DIRV, RM, GENV, SV, TLV, WINV, NTLV)                                            \
+#define BDSP_PASS_K(DIRV, RM, GENV, SV, WINV, NTLV)                                                 \
     do {                                                                                           \
         constexpr size_t lds = pass_tile_lds_bytes<T, RP, W, GENV>() +                             \
                                (pass_lds_twiddles<T, RP, W, GENV>() ? (size_t)RP * sizeof(cpx<T>) : 0); \
-        BDSP_TRY(set_lds(k_fft_pass<T, RP, W, DIRV, RM, GENV, SV, TLV, WINV, NTLV>, lds));         \
-        hipLaunchKernelGGL((k_fft_pass<T, RP, W, DIRV, RM, GENV, SV, TLV, WINV, NTLV>), grid, dim3(THREADS), lds, s, \
-                           io, src, dst, wtab, n, nsg, tiles, (int)last, aux);                     \
+        BDSP_TRY(set_lds(k_fft_pass<T, RP, W, DIRV, RM, GENV, SV, WINV, NTLV>, lds));              \
+        hipLaunchKernelGGL((k_fft_pass<T, RP, W, DIRV, RM, GENV, SV, WINV, NTLV>), grid, dim3(THREADS), lds, s, \
+                           io, src, dst, wtab, n, nsg, tiles, (int)last);                          \
     } while (0)
-#define BDSP_PASS(DIRV, RM, GENV, SV, TLV, WINV)                                                   \
+#define BDSP_PASS(DIRV, RM, GENV, SV, WINV)                                                        \
     do {                                                                                           \
-        if constexpr (pass_ntl_candidate<T, RP, W>() && RM && !GENV && TLV == 0) {                 \
-            if (ntl) { BDSP_PASS_K(DIRV, RM, GENV, SV, TLV, WINV, true); break; }                  \
+        if constexpr (pass_ntl_candidate<T, RP, W>() && RM && !GENV) {                             \
+            if (ntl) { BDSP_PASS_K(DIRV, RM, GENV, SV, WINV, true); break; }                       \
         }                                                                                          \
-        BDSP_PASS_K(DIRV, RM, GENV, SV, TLV, WINV, false);                                         \
+        BDSP_PASS_K(DIRV, RM, GENV, SV, WINV, false);                                              \
     } while (0)
 #if BDSP_FFT_PART == 1
-#define BDSP_PASS_V(DIRV, RM, TLV) BDSP_PASS(DIRV, RM, false, true, TLV, -1) /* (everything else went to the options unit above) */
+#define BDSP_PASS_V(DIRV, RM) BDSP_PASS(DIRV, RM, false, true, -1) /* (everything else went to the options unit above) */
 #else
 #if BDSP_FFT_PART == 2
-#define BDSP_PASS_SIMPLE(DIRV, RM, TLV) do { set_last_error("plain pass in the options unit"); return BDSP_ERR_UNSUPPORTED; } while (0)
+#define BDSP_PASS_SIMPLE(DIRV, RM) do { set_last_error("plain pass in the options unit"); return BDSP_ERR_UNSUPPORTED; } while (0)
 #else
-#define BDSP_PASS_SIMPLE(DIRV, RM, TLV) BDSP_PASS(DIRV, RM, false, true, TLV, -1)
+#define BDSP_PASS_SIMPLE(DIRV, RM) BDSP_PASS(DIRV, RM, false, true, -1)
 #endif
-#define BDSP_PASS_V(DIRV, RM, TLV)                                                                 \
+#define BDSP_PASS_V(DIRV, RM)                                                                      \
     do {                                                                                           \
-        if (gen) BDSP_PASS(DIRV, RM, true, false, TLV, -1);                                        \
-        else if (simple) BDSP_PASS_SIMPLE(DIRV, RM, TLV);                                          \
+        if (gen) BDSP_PASS(DIRV, RM, true, false, -1);                                             \
+        else if (simple) BDSP_PASS_SIMPLE(DIRV, RM);                                               \
         else {                                                                                     \
-            if constexpr (pass_split_exchange<T, RP, W, false>() && TLV == 0) {                    \
-                if (win_fixed == 0) { BDSP_PASS(DIRV, RM, false, false, TLV, 0); break; }          \
-                if (win_fixed == 2) { BDSP_PASS(DIRV, RM, false, false, TLV, 2); break; }          \
+            if constexpr (pass_split_exchange<T, RP, W, false>()) {                                \
+                if (win_fixed == 0) { BDSP_PASS(DIRV, RM, false, false, 0); break; }               \
+                if (win_fixed == 2) { BDSP_PASS(DIRV, RM, false, false, 2); break; }               \
             }                                                                                      \
-            BDSP_PASS(DIRV, RM, false, false, TLV, -1);                                            \
+            BDSP_PASS(DIRV, RM, false, false, -1);                                                 \
         }                                                                                          \
     } while (0)
 #endif
 #define BDSP_PASS_D(DIRV)                                                                          \
     do {                                                                                           \
-        if constexpr (pass_tiled_pair<RP>()) {                                                     \
-            if (tl == 1) { BDSP_PASS_V(DIRV, true, 1); break; }                                    \
-            if (tl == 2) { BDSP_PASS_V(DIRV, false, 2); break; }                                   \
-        }                                                                                          \
-        if (rowmap) BDSP_PASS_V(DIRV, true, 0);                                                    \
+        if (rowmap) BDSP_PASS_V(DIRV, true);                                                       \
         else if constexpr (pass_first_only<RP, W>()) { set_last_error("first-pass-only tile"); return BDSP_ERR_UNSUPPORTED; } \
-        else BDSP_PASS_V(DIRV, false, 0);                                                          \
+        else BDSP_PASS_V(DIRV, false);                                                             \
     } while (0)
     if (inverse) BDSP_PASS_D(1); else BDSP_PASS_D(-1);
 #undef BDSP_PASS_D
@@ -1146,49 +950,22 @@ static int launch_pass(const FftIo<T>& io_in, const cpx<T>* src, cpx<T>* dst, si
     return BDSP_OK;
 }
 
-// the two launches of k_fft_half512 for ONE plain 2^20-point f32 vector (io.in -> scratch_a -> io.out)
-#if defined(BDSP_FFT_F32_TU) && defined(BDSP_LAB)
-static int launch_half512(const FftIo<float>& io, cpx<float>* mid, bool inverse, hipStream_t s)
-{
-    const cpx<float>* wtab;
-    BDSP_TRY(twiddle_table<float>(1024, &wtab));
-    constexpr size_t lds = ((size_t)4 * col_stride(512, 4) + 1024) * sizeof(cpx<float>);
-    const cpx<float>* in = reinterpret_cast<const cpx<float>*>(io.in);
-    cpx<float>* out = reinterpret_cast<cpx<float>*>(io.out);
-    if (inverse) {
-        hipLaunchKernelGGL((k_fft_half512<1, true>), dim3(512), dim3(256), lds, s, io, in, mid, wtab);
-        hipLaunchKernelGGL((k_fft_half512<1, false>), dim3(512), dim3(256), lds, s, io, mid, out, wtab);
-    } else {
-        hipLaunchKernelGGL((k_fft_half512<-1, true>), dim3(512), dim3(256), lds, s, io, in, mid, wtab);
-        hipLaunchKernelGGL((k_fft_half512<-1, false>), dim3(512), dim3(256), lds, s, io, mid, out, wtab);
-    }
-    BDSP_LAUNCH_CHECK();
-    return BDSP_OK;
-}
-#else
-template <typename T>
-static int launch_half512(const FftIo<T>&, cpx<T>*, bool, hipStream_t) { return BDSP_ERR_UNSUPPORTED; } // (LAB build, f32 TU only)
-#endif
-
 // (super-radix, tile width) pairs that are instantiated.  Default tile: W = 4096/RP columns
 // (256 threads); the wider variants trade LDS for longer contiguous global segments.
 template <typename T>
 static int launch_pass_rp(int rp, int w, const FftIo<T>& io, const cpx<T>* src, cpx<T>* dst,
                           size_t n, size_t nsg, size_t batch, bool inverse, bool first, bool last,
-                          hipStream_t s, int tl = 0, int aux = 0)
+                          hipStream_t s)
 {
 #define BDSP_CASE(RPV, WV)                                                                         \
     if (rp == RPV && w == WV)                                                                      \
-        return launch_pass<T, RPV, WV>(io, src, dst, n, nsg, batch, inverse, first, last, s, tl, aux);
-    // every pair plan_passes can choose by itself ...
+        return launch_pass<T, RPV, WV>(io, src, dst, n, nsg, batch, inverse, first, last, s);
+    // every pair plan_passes can choose
     BDSP_CASE(64, 64) BDSP_CASE(128, 32) BDSP_CASE(256, 16) BDSP_CASE(512, 8) BDSP_CASE(1024, 4)
     BDSP_CASE(1024, 8) BDSP_CASE(2048, 4)
-    // (the first pass of 2^22 f32 points, round 5: the ROWMAP instantiations only, see pass_first_only)
+    // (the first pass of 2^22 f32 points, round 5: the ROWMAP instantiations only, see pass_first_only; f64 4096 x 4 tiles spill
+    // 12-76 bytes per lane)
     if constexpr (sizeof(T) == 4) { BDSP_CASE(4096, 4) }
-#ifdef BDSP_LAB
-    // ... and the ones only a BDSP_FFT_PLAN experiment reaches (the f64 4096 x 4 tiles spill 12-76 bytes per lane)
-    BDSP_CASE(2048, 2) BDSP_CASE(4096, 2) BDSP_CASE(4096, 4) BDSP_CASE(1024, 2)
-#endif
 #undef BDSP_CASE
     set_last_error("unsupported super-radix / tile width");
     return BDSP_ERR_UNSUPPORTED;
@@ -1202,22 +979,9 @@ static int plan_passes(size_t n, size_t batch, size_t esz, int rp[3], int w[3])
     int bits = 0;
     while ((size_t(1) << bits) < n) ++bits;
     if (bits > 30) return 0;
-    // experiment hook (lab build only): BDSP_FFT_PLAN="4096x2,4096x2" (radix x tile width per pass)
-    if (const char* e = lab_env("BDSP_FFT_PLAN")) {
-        int k = 0;
-        size_t prod = 1;
-        while (*e && k < 3) {
-            int r = 0, ww = 0;
-            if (sscanf(e, "%dx%d", &r, &ww) != 2) break;
-            rp[k] = r; w[k] = ww; prod *= (size_t)r; ++k;
-            while (*e && *e != ',') ++e;
-            if (*e == ',') ++e;
-        }
-        if (k >= 2 && prod == n) return k;
-    }
     // 2^21 and 2^22 points: two passes of long columns beat three fully coalesced ones although their runs are only 32-64
-    // bytes.  Round 5, re-measured on VALID data with input and scratch cold / input in the caches (tools/plan_probe.py,
-    // profiles/r05_plan_probe_valid.txt; the figures of rounds 2-3 came from loops that transformed their own output, i.e.
+    // bytes.  Round 5, re-measured on VALID data with input and scratch cold / input in the caches
+    // (profiles/r05_plan_probe_valid.txt; the figures of rounds 2-3 came from loops that transformed their own output, i.e.
     // inf / NaN), last pass in place:
     //   2^21 f32  1024x8 + 2048x4  24.3 / 19.8 us   (2048x4 + 1024x8 24.6 / 19.2; three passes 30.3 / 26.9 out of place)
     //   2^22 f32  4096x4 + 1024x8  40.4 / 32.3      (2048x4 + 2048x4, the plan until round 5: 42.9 / 33.3; three passes 41.4 / 34.0)
@@ -1254,8 +1018,7 @@ static int plan_passes(size_t n, size_t batch, size_t esz, int rp[3], int w[3])
 template <typename T>
 static bool wg4_serves(size_t n)
 {
-    static const bool no_wg4 = lab_flag("BDSP_FFT_NO_WG4");
-    return sizeof(T) == 4 && n == 8192 && !no_wg4;
+    return sizeof(T) == 4 && n == 8192;
 }
 
 // Runs the transform described by `io` on power-of-two n.  io.in holds the input.  For n <= 4096
@@ -1296,15 +1059,6 @@ int fft_pow2(const FftIo<T>& io, T* scratch_a, T* scratch_b, size_t batch, bool 
         if (wg4_serves<T>(n) && !io_is_generic(io) && io.window_id < 0 &&
             !(io.flags & (BDSP_FFT_MAGNITUDE | FFT_OUT_REAL | FFT_IN_REAL))) return launch_wg4<T, 8192>(io, batch, inverse, s);
     }
-    if constexpr (sizeof(T) == 4) {
-        // ONE plain 2^20-point vector (config C2) through the half-column plan: LAB experiment only (*measured* slower,
-        // round 4)
-        static const bool h512 = lab_flag("BDSP_FFT_H512");
-        if (h512 && n == (size_t(1) << 20) && batch == 1 && scratch_a && !io_is_generic(io) && io.window_id < 0 && io.in_scale == (T)1 &&
-            !(io.flags & (FFT_IN_REAL | BDSP_FFT_SHIFT_IN)) && io.in_valid == 0 &&
-            reinterpret_cast<const void*>(scratch_a) != io.in && reinterpret_cast<const void*>(scratch_a) != io.out)
-            return launch_half512(io, reinterpret_cast<cpx<T>*>(scratch_a), inverse, s);
-    }
     int rp[3], w[3];
     int passes = plan_passes(n, batch, sizeof(T), rp, w);
     if (passes == 0) { set_last_error("FFT length above 2^30 points"); return BDSP_ERR_UNSUPPORTED; }
@@ -1315,22 +1069,12 @@ int fft_pow2(const FftIo<T>& io, T* scratch_a, T* scratch_b, size_t batch, bool 
     cpx<T>* sa = reinterpret_cast<cpx<T>*>(scratch_a);
     cpx<T>* sb = reinterpret_cast<cpx<T>*>(scratch_b);
     size_t nsg = 1;
-    // two passes with narrow second-pass tiles: the intermediate through scratch_a in the TILED layout (k_fft_pass, TL) --
-    // LAB experiment (BDSP_FFT_TILED=1).  *Measured*, round 4 (tools/ab_tiled.sh, profiles/r04_fft_tiled_intermediate.txt):
-    // the second pass's reads become one contiguous block per tile, the first pass's stores 128-512-byte pieces instead of
-    // whole 4-8 KB columns, and nothing gets faster -- C2 17.1 -> 17.5 us, C2 x 64 384 -> 409, C4a 53.2 -> 54.0, C5 equal:
-    // the narrow READS were never the cost (32-byte sectors out of the Infinity Cache), and the scattered stores are one.
-    static const bool want_tiled = lab_flag("BDSP_FFT_TILED");
-    // (not with the triangular / Blackman-Harris window: the split-exchange f64 tiles carry those as per-window
-    // instantiations, which exist for the natural-order intermediate only -- a tiled one would silently apply Hamming)
-    const bool tiled = passes == 2 && want_tiled && rp[0] >= 512 && rp[1] >= 512 && (size_t)w[1] * sizeof(cpx<T>) < 128 &&
-                       reinterpret_cast<const void*>(scratch_a) != io.out && io.window_id != 0 && io.window_id != 2;
-    int lw2 = 0;
-    while ((1 << lw2) < w[1]) ++lw2;
-    BDSP_TRY(launch_pass_rp<T>(rp[0], w[0], io, nullptr, sa, n, nsg, batch, inverse, true, false, s, tiled ? 1 : 0, lw2));
+    // (the intermediate in natural order: a tiled layout, one contiguous block per second-pass tile, measured no faster --
+    // round 4, profiles/r04_fft_tiled_intermediate.txt: the narrow reads were never the cost, its scattered stores are one)
+    BDSP_TRY(launch_pass_rp<T>(rp[0], w[0], io, nullptr, sa, n, nsg, batch, inverse, true, false, s));
     nsg *= rp[0];
     if (passes == 2) {
-        BDSP_TRY(launch_pass_rp<T>(rp[1], w[1], io, sa, nullptr, n, nsg, batch, inverse, false, true, s, tiled ? 2 : 0, 0));
+        BDSP_TRY(launch_pass_rp<T>(rp[1], w[1], io, sa, nullptr, n, nsg, batch, inverse, false, true, s));
     } else {
         BDSP_TRY(launch_pass_rp<T>(rp[1], w[1], io, sa, sb, n, nsg, batch, inverse, false, false, s));
         nsg *= rp[1];
@@ -1360,9 +1104,9 @@ int fft_pow2_plain_trips(size_t n)
 // the options unit's two entry points (with BDSP_FFT_PART == 0 they are defined here too and simply never called)
 template <typename T>
 int launch_pass_opts_rp(int rp, int w, const FftIo<T>& io, const cpx<T>* src, cpx<T>* dst, size_t n, size_t nsg, size_t batch,
-                        bool inverse, bool first, bool last, hipStream_t s, int tl, int aux)
+                        bool inverse, bool first, bool last, hipStream_t s)
 {
-    return launch_pass_rp<T>(rp, w, io, src, dst, n, nsg, batch, inverse, first, last, s, tl, aux);
+    return launch_pass_rp<T>(rp, w, io, src, dst, n, nsg, batch, inverse, first, last, s);
 }
 template <typename T>
 int launch_wg_gen(int n, const FftIo<T>& io, size_t batch, bool inverse, hipStream_t s)
@@ -1385,7 +1129,7 @@ int launch_wg_gen(int n, const FftIo<T>& io, size_t batch, bool inverse, hipStre
 #endif
 #if BDSP_FFT_PART == 2
 template int launch_pass_opts_rp<BDSP_FFT_T>(int, int, const FftIo<BDSP_FFT_T>&, const cpx<BDSP_FFT_T>*, cpx<BDSP_FFT_T>*, size_t, size_t, size_t, bool, bool,
-                                             bool, hipStream_t, int, int);
+                                             bool, hipStream_t);
 template int launch_wg_gen<BDSP_FFT_T>(int, const FftIo<BDSP_FFT_T>&, size_t, bool, hipStream_t);
 #else
 template int fft_pow2<BDSP_FFT_T>(const FftIo<BDSP_FFT_T>&, BDSP_FFT_T*, BDSP_FFT_T*, size_t, bool, hipStream_t);

@@ -840,9 +840,8 @@ int interpolatef_dev(const T* in, T* out, size_t len, bool is_complex, int fid, 
         // k_interp_scalar_v2 wherever the cos / sin table of the roll-off lattice fits 48 KB of LDS (every practical conv_len:
         // up to 3071 taps a side in f32, 1535 in f64) and positions fit 32 bits; otherwise the first-generation kernel
         // (tests/test_gpu_parity.py::test_interpolatef_fractional_factor_kernel_singularities_and_fallback runs both)
-        static const bool no_pk = lab_flag("BDSP_INTERP_NO_PK"); // (LAB: A/B against k_interp_scalar_v2)
         // at most 127 taps (the slow-pair mask is one 64-bit word; above: k_interp_scalar_v2)
-        if (!no_pk && 2 * conv_len + 1 <= 127 && points < ((size_t)1 << 31)) {
+        if (2 * conv_len + 1 <= 127 && points < ((size_t)1 << 31)) {
             const unsigned long long slow = frac_slow_pairs(conv_len, (double)delay, fid, (double)rolloff);
             const size_t lds = sizeof(T) * 2 * ((2 * conv_len + 1 + 3) & ~(size_t)3);
             if (is_complex)

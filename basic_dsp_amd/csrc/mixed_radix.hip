@@ -18,7 +18,6 @@
 #include "dsp_funcs.h"
 #include "mr_dft.h"
 #include <algorithm>
-#include <cstdlib>
 #include <mutex>
 #include <unordered_map>
 #include <vector>
@@ -351,8 +350,8 @@ template <typename T> static int mr_tile() { return sizeof(T) == 4 ? 8 : 4; }   
 // longest sub-transform a tile of W lanes can hold: 2 ping-pong buffers of len * W points + the table
 template <typename T> static size_t mr_pass_max(int W) { return MR_LDS_BYTES / (sizeof(cpx<T>) * (2 * W + 1)); }
 
-// Four-step or three Stockham passes?  *Measured* (round 5, tools/plan_probe.py --points, cold us, LAB switch BDSP_MR_PLAN;
-// profiles/r05_plan_probe_valid.txt run 13, after the index arithmetic lost its divisions): while the four-step's tile is 8
+// Four-step or three Stockham passes?  *Measured* (round 5, cold us, profiles/r05_plan_probe_valid.txt run 13, after the
+// index arithmetic lost its divisions): while the four-step's tile is 8
 // wide it wins (10^6 points f32 32 against 49 us, f64 34 against 65 at its widest tile of 4; 64 x 10^5 f32 126 against 184);
 // at 4-wide f32 tiles it depends on the factors (3 * 10^6 79 against 87, 1.5 * 10^6 60 against 54) and the four-step keeps
 // them; at 2-wide tiles three passes win or tie everywhere -- f32 6 * 10^6 210 -> 180, 10^7 356 -> 280, 1.296 * 10^7 426 -> 307;
@@ -367,10 +366,9 @@ constexpr size_t MR_PLAN3_MIN = 100000;
 template <typename T>
 static bool mr_split(size_t n, size_t* n1, size_t* n2, int* wmax)
 {
-    // (LAB, BDSP_MR_W1: also single-column tiles -- measured in round 5: they beat the chirp-z path that served such lengths
-    // until then (f64 3 * 10^6 points 400 -> 236 us) and lose to three Stockham passes (130 us), which is what runs now)
-    static const bool w1 = lab_flag("BDSP_MR_W1");
-    for (int W = mr_tile<T>(); W >= (w1 ? 1 : 2); W /= 2) {
+    // (no single-column tiles -- measured in round 5: they beat the chirp-z path that served such lengths until then
+    // (f64 3 * 10^6 points 400 -> 236 us) and lose to three Stockham passes (130 us), which is what runs now)
+    for (int W = mr_tile<T>(); W >= 2; W /= 2) {
         const size_t pm = mr_pass_max<T>(W);
         if (n > pm * pm) continue;
         size_t best = 0;
@@ -410,8 +408,9 @@ static bool mr_split3(size_t n, size_t r[3], int* wmax)
     }
     if (!best) return false;
     r[0] = b0; r[1] = b1; r[2] = b2;
-    // (*measured*, BDSP_MR_W3: f64 3 / 6 / 10 * 10^6 points 157 / 315 / 499 us at 16-wide tiles, 172 / 318 / 473 at 8, 143 / 282 / 460 at
-    // 4; f32 2 / 3 * 10^7 714 / 1003 at 16, 627 / 936 at 8, 657 / 992 at 4: the 64-byte tile of the four-step form)
+    // (*measured* with the tile width forced: f64 3 / 6 / 10 * 10^6 points 157 / 315 / 499 us at 16-wide tiles, 172 / 318 / 473
+    // at 8, 143 / 282 / 460 at 4; f32 2 / 3 * 10^7 714 / 1003 at 16, 627 / 936 at 8, 657 / 992 at 4: the 64-byte tile of the
+    // four-step form)
     int W = mr_tile<T>();
     while (W > 2 && mr_pass_max<T>(W) < b0) W /= 2;
     *wmax = W;
@@ -433,12 +432,9 @@ static int mr_global_plan(size_t n, size_t* n1, size_t* n2, int* w2, size_t r3[3
         auto it = cache.find(n);
         if (it != cache.end()) p = it->second;
         else {
-            static const int forced = [] { const char* e = lab_env("BDSP_MR_PLAN"); return e ? atoi(e) : 0; }();
             const bool ok2 = mr_split<T>(n, &p.n1, &p.n2, &p.w2);
             const bool ok3 = n >= (size_t)MR_PLAN3_MIN && mr_split3<T>(n, p.r3, &p.w3);
-            if (forced == 2 && ok2) p.plan = 2;
-            else if (forced == 3 && ok3) p.plan = 3;
-            else if (ok2 && (p.w2 >= mr_plan2_min_tile<T>() || !ok3)) p.plan = 2;
+            if (ok2 && (p.w2 >= mr_plan2_min_tile<T>() || !ok3)) p.plan = 2;
             else if (ok3) p.plan = 3;
             else p.plan = ok2 ? 2 : 0;
             if (cache.size() < 4096) cache[n] = p;
@@ -573,8 +569,6 @@ int mr_fft(const T* in, T* out, T* scratch, size_t n, size_t batch, bool inverse
         cpx<T>* bufs[2] = {reinterpret_cast<cpx<T>*>(scratch), reinterpret_cast<cpx<T>*>(const_cast<T*>(in))};
         if (out != scratch) { set_last_error("mixed radix, three passes: the result goes to the scratch buffer"); return BDSP_ERR_UNSUPPORTED; }
         int W = w3;
-        static const int w3_env = [] { const char* e = lab_env("BDSP_MR_W3"); return e ? atoi(e) : 0; }();
-        if (w3_env > 0 && w3_env <= w3) W = w3_env;
         while (W & (W - 1)) W &= W - 1;
         unsigned long long nsg = 1;
         const cpx<T>* src = nullptr;
@@ -613,8 +607,6 @@ int mr_fft(const T* in, T* out, T* scratch, size_t n, size_t batch, bool inverse
     int W = wmax;
     const int wmin = wmax < 2 ? 1 : (n >= 200000 ? 4 : 2); // *measured* 10^6 points: W = 8 / 4 / 2 -> 45.7 / 36.5 / 48.5 us; 10^5: 18.0 / 14.7 / 14.1
     while (W > wmin && ((n2 + W - 1) / W) * batch < (size_t)num_cus()) W /= 2;
-    static const int w_env = [] { const char* e = lab_env("BDSP_MR_W"); return e ? atoi(e) : 0; }();
-    if (w_env > 0 && w_env <= wmax) W = w_env;
     while (W & (W - 1)) W &= W - 1; // (the kernels index a tile by shifts: a power of two)
     const size_t lds1 = sizeof(cpx<T>) * (2 * n1 * W + n1), lds2 = sizeof(cpx<T>) * (2 * n2 * W + n2);
     cpx<T>* tmp = reinterpret_cast<cpx<T>*>(scratch);

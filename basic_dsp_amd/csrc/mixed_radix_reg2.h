@@ -157,8 +157,6 @@ static int mr_reg2_run(const MrReg3Io<T>& io, size_t batch, bool inverse, hipStr
 template <typename T>
 int mr_reg2_launch(const MrReg3Io<T>& io, size_t n, size_t batch, bool inverse, hipStream_t s)
 {
-    static const bool off = lab_flag("BDSP_MR_NO_REG3");
-    if (off) return MR_REG3_NOT_BUILT;
 #define BDSP_REG2(NV, A, B_) case NV: return mr_reg2_run<T, A, B_>(io, batch, inverse, s);
     switch (n) {
     BDSP_REG2(20, 5, 4)

@@ -23,7 +23,7 @@ namespace bdsp {
 //   Exchange B (stage 1 -> 2): thread j writes (j / R0) R0 R1 + j mod R0 + r R0; groups are SB = R0 R1 + pad apart with
 //       SB = R0 (mod 32), so the runs of R0 lanes tile the banks; stage 2 reads r SB + j.
 //   Every LDS address is a per-thread base plus a compile-time offset.  Two buffers, two barriers per transform.
-// *Measured* (tools/plan_probe.py, valid data, cold / hot us, against k_mr_wg; profiles/r06_plan_probe_valid.txt): f32 16384 x 1000
+// *Measured* (valid data, cold / hot us, against k_mr_wg; profiles/r06_plan_probe_valid.txt): f32 16384 x 1000
 // points 136 / 115 -> 57 / 56 (0.24 -> 0.59 of the HBM roofline), 8192 x 2000 195 / 159 -> 57 / 53, 4096 x 3600 348 / 311 -> 51 / 49,
 // 4096 x 3000 (512 threads) 173 / 146 -> 45 / 46, ONE 1000-point transform 7.5 / 4.8 -> 3.8 / 2.7; f64 16384 x 1000 257 / 252 -> 102 / 85,
 // 8192 x 2000 498 / 489 -> 104 / 93.
@@ -196,9 +196,6 @@ static int mr_reg3_run(const MrReg3Io<T>& io, size_t batch, bool inverse, hipStr
         occ = o;
     }
     const size_t groups = (batch + P::B - 1) / P::B, slots = (size_t)num_cus() * (size_t)occ;
-    // (LAB: BDSP_MR_REG3_ROUNDS = r sends batches of fewer than r rounds of persistent workgroups to k_mr_wg instead)
-    static const int min_rounds = [] { const char* e = lab_env("BDSP_MR_REG3_ROUNDS"); return e ? atoi(e) : 0; }();
-    if (groups < (size_t)min_rounds * slots) return MR_REG3_NOT_BUILT;
     const unsigned grid = (unsigned)(groups < slots ? groups : slots);
     if constexpr (P::THREADS == 512 && sizeof(T) == 4) {
         if (io.plain) { // the plain-only instantiation: two workgroups per CU (see k_mr_reg3 OPTS)
@@ -233,8 +230,6 @@ static int mr_reg3_run(const MrReg3Io<T>& io, size_t batch, bool inverse, hipStr
 template <typename T>
 int mr_reg3_launch(const MrReg3Io<T>& io, size_t n, size_t batch, bool inverse, hipStream_t s)
 {
-    static const bool off = lab_flag("BDSP_MR_NO_REG3");
-    if (off) return MR_REG3_NOT_BUILT;
 #define BDSP_REG3(NV, A, B_, C_) case NV: return mr_reg3_run<T, A, B_, C_>(io, batch, inverse, s);
     switch (n) {
     BDSP_REG3(300, 10, 6, 5)

@@ -85,8 +85,7 @@ def test_is_supported_fft_len_contract():
 
 
 def test_the_product_library_reads_no_environment_variable():
-    """Experiment switches live in the LAB build only (make -C basic_dsp_amd/csrc lab): the shipped library does not even
-    import getenv."""
+    """The library has no experiment switches: the shipped library does not even import getenv."""
     import subprocess
     import basic_dsp_amd._lib as L
     if os.path.basename(L.LIB_PATH) != "libbasic_dsp_hip.so":

@@ -13,9 +13,8 @@ the caller's own CPU code wins.  This tool measures, on the box it runs on:
         exactly what runs when the plug-in declines) and through numpy / scipy (pocketfft: "sanity", NOT the reference --
         it stands in for a tuned CPU FFT such as rustfft, so the policy is set against the FASTER of the two CPU rows)
 
-for every staging mode of the LAB library (BDSP_B1_STAGE = 0 pageable copies, 1 pinned copies, 2 kernels read the pinned
-stage, 3 kernels read and write it) and for the product library as shipped.  The parent process never touches the GPU; each
-variant runs in a child.  Output: a table on stdout and JSON lines in --out.
+for the product library as shipped.  The parent process never touches the GPU; each variant runs in a child.  Output: a
+table on stdout and JSON lines in --out.
 
     python3 tools/b1_crossover.py --out gpurun_out/r06_b1/crossover.jsonl > gpurun_out/r06_b1/crossover.txt
 """
@@ -190,7 +189,6 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--child-timeout", type=int, default=900)
     ap.add_argument("--what", default="fft,conv")
-    ap.add_argument("--no-lab", action="store_true")
     args = ap.parse_args()
     if args.child:
         if args.label.startswith("cpu"):
@@ -198,10 +196,7 @@ def main():
         else:
             child_gpu(args.child, args.label, args)
         return
-    lab = os.path.join(ROOT, "basic_dsp_amd", "lib", "libbasic_dsp_hip_lab.so")
     variants = [("product", {})]
-    if os.path.exists(lab) and not args.no_lab:
-        variants += [("lab_stage%d" % k, {"BDSP_HIP_LIBRARY": lab, "BDSP_B1_STAGE": str(k)}) for k in (0, 1, 2, 3)]
     rows = []
     for what in args.what.split(","):
         rows += run_child(what, "cpu", {"OMP_NUM_THREADS": "1"}, args)

@@ -2,7 +2,7 @@
 """Round 6's new kernels on valid data, a few launches each, for rocprofv3 (tools/profile_new_kernels.sh): k_mr_reg3 (16384 x 1000
 and 4096 x 3000 points f32, 16384 x 1000 f64), k_mr_reg2 (65536 x 100 points f32), k_interp_frac_pk (4M -> 10M complex points, factor
 2.5, conv_len 12: sinc and raised cosine, f32 and f64).  Every transform runs on a buffer that was restored from a pristine copy of
-the random input just before it (valid data, input in the caches: the "hot" protocol of tools/plan_probe.py), forty times per
+the random input just before it (valid data, input in the caches: the "hot" protocol of profiles/r05_plan_probe_valid.txt), forty times per
 configuration so that the kernel trace's average is taken at the sustained clock, not on the ramp."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

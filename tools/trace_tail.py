@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Average duration of the LAST k calls' dispatches of every kernel whose name contains `pattern`, from a rocprofv3
---kernel-trace CSV directory:  python tools/trace_tail.py <dir> <k> <pattern>.  With tools/plan_probe.py --only cold the
-last k calls of the process are its cold ones, so this splits a cold transform into its passes (kernels in launch order; a
-kernel that serves several passes of one call is averaged over all of them)."""
+--kernel-trace CSV directory:  python tools/trace_tail.py <dir> <k> <pattern>.  When the last k calls of the process are its
+cold ones, this splits a cold transform into its passes (kernels in launch order; a kernel that serves several passes of one
+call is averaged over all of them)."""
 import csv, glob, os, sys
 d, k, pat = sys.argv[1], int(sys.argv[2]), sys.argv[3]
 rows = []

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Is a vector that was just UPLOADED (overwrite_data: a host-to-device copy) cold for the first pass of its transform?
 Through the facade (B2), f64 4M points windowed_fft(Hann) and plain_fft at a few sizes: the upload, a synchronise, then one
-event pair on the library's stream around the call; median of 15.  Run once per library (BDSP_HIP_LIBRARY): the LAB build
-against the one whose first pass loads non-temporally (libbasic_dsp_hip_lab_ntload2.so)."""
+event pair on the library's stream around the call; median of 15.  Works on any library: run it once per build to compare
+(BDSP_HIP_LIBRARY)."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
