@@ -292,6 +292,11 @@ for _s, _t, _R in (("32", _F, VectorInteropResult32), ("64", _D, VectorInteropRe
             _proto(_m + _n + "_dot_product" + _v + _s, C.c_int32, _P, _P, C.POINTER(_o), _SZ)
             _proto(_m + _n + "_dot_product" + _v + "_prec" + _s, C.c_int32, _P, _P,
                    C.POINTER(_D if _n == "real" else Complex64), _SZ)
+    # cross correlation of the rows
+    for _n in ("prepare_argument", "prepare_argument_padded"):
+        _proto(_m + _n + _s, C.c_int32, _P)
+    for _n in ("correlate", "correlate_vector"):
+        _proto(_m + _n + _s, C.c_int32, _P, _P)
 
 WINDOW_FN32 = C.CFUNCTYPE(_F, _P, _SZ, _SZ)
 WINDOW_FN64 = C.CFUNCTYPE(_D, _P, _SZ, _SZ)

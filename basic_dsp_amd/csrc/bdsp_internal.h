@@ -253,6 +253,15 @@ template <typename T>
 int mr_dot(const T* x, size_t xstride, const T* y, size_t ystride, size_t rows, size_t n, bool cplx, int kind,
            void* out, hipStream_t s);
 
+// mat_correlate.hip -- cross-correlation of the rows of a matrix with a prepared argument
+// every row Surround-padded from p to l elements (complex pairs if is_complex), out of place, one launch
+template <typename T> int mc_pad_rows(const T* in, T* out, size_t rows, size_t p, size_t l, bool is_complex, hipStream_t s);
+bool mc_fused_len(size_t l); // a power of two in [16, 4096]: mc_correlate_fused applies
+// rows x p complex points -> rows x l: pad, transform, x arg (row r at arg + r * arg_stride complex points; 0 = one
+// argument for every row), inverse transform, 1/l, swap_halves -- one launch; in and out must not overlap
+template <typename T>
+int mc_correlate_fused(const T* in, T* out, const T* arg, size_t arg_stride, size_t rows, size_t p, size_t l, hipStream_t s);
+
 // bluestein.hip
 template <typename T> int bs_chirp(T* c, size_t n, bool inverse, hipStream_t s);
 template <typename T> int bs_kernel(const T* c, T* b, size_t n, size_t m, hipStream_t s);

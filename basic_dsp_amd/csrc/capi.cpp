@@ -1995,6 +1995,66 @@ int mat_dot_vec(const DevMat<T>* m, const DevVec<T>* o, bool cplx, int kind, siz
     return mat_dot<T>(m, o, m->rows, 0, o->valid_len, cplx, kind, elem_bytes, out, out_len);
 }
 
+// Cross correlation of the rows (matrix/src/time_freq.rs:208-264 forwards correlation.rs:96-160 row by row): every row
+// behaves as op_prepare_argument / op_correlate would on it, with launch counts that do not depend on the row count.
+template <typename T>
+int mat_pad_surround(DevMat<T>* m, size_t points)
+{
+    const size_t step = m->v.complex_ ? 2 : 1, p = m->row_points();
+    BDSP_TRY(m->v.reserve(m->rows * points * step));
+    BDSP_TRY(mc_pad_rows<T>(m->v.data, m->v.buf, m->rows, p, points, m->v.complex_, lib_stream()));
+    m->v.trade();
+    m->v.valid_len = m->rows * points * step;
+    return BDSP_OK;
+}
+
+template <typename T>
+int mat_prepare_argument(DevMat<T>* m, bool padded)
+{
+    if (padded) {
+        const size_t p = m->row_points();
+        if (p <= 1) return BDSP_ERR_ARG_LENGTH; // as op_prepare_argument
+        BDSP_TRY(mat_pad_surround<T>(m, 2 * p - 1));
+    }
+    BDSP_TRY(op_fft<T>(&m->v, false, false, -1, m->rows ? m->rows : 1));
+    if (m->v.erroneous()) return BDSP_OK;
+    return ew_conj<T>(m->v.data, m->v.valid_len, lib_stream());
+}
+
+// other: `o_rows` prepared rows of `l` points each, `arg_stride` complex points apart (0: one vector for every row)
+template <typename T>
+int mat_correlate(DevMat<T>* m, const DevVec<T>* o, size_t o_rows, size_t l, size_t arg_stride)
+{
+    if (m->v.freq || !m->v.complex_ || !o->freq || !o->complex_) { // correlation.rs:134-146
+        m->v.poison(); m->v.complex_ = true; m->v.freq = true;
+        return BDSP_ERR_MUST_BE_TIME;
+    }
+    if (o_rows != m->rows) return BDSP_ERR_ARG_LENGTH; // as mat_binary
+    const size_t rows = m->rows, p = m->row_points();
+    if (rows == 0) return BDSP_OK;
+    if (l <= p) return BDSP_ERR_ARG_LENGTH; // zero_pad: the argument must be longer than the rows
+    hipStream_t s = lib_stream();
+    BDSP_TRY(m->v.reserve(rows * 2 * l));
+    if (mc_fused_len(l)) {
+        BDSP_TRY(mc_correlate_fused<T>(m->v.data, m->v.buf, o->data, arg_stride, rows, p, l, s));
+        m->v.trade();
+        m->v.valid_len = rows * 2 * l;
+        return BDSP_OK;
+    }
+    BDSP_TRY(mc_pad_rows<T>(m->v.data, m->v.buf, rows, p, l, true, s));
+    m->v.trade();
+    m->v.valid_len = rows * 2 * l;
+    bool in_b = false;
+    BDSP_TRY(fft_two_buffers<T>(m->v.data, m->v.buf, l, rows, false, 0, (T)1, -1, (T)0, &in_b, s));
+    if (in_b) m->v.trade();
+    if (arg_stride) BDSP_TRY(ew_binary<T>(m->v.data, o->data, m->v.valid_len, true, 2, s));
+    else BDSP_TRY(ew_binary_smaller<T>(m->v.data, o->data, m->v.valid_len, 2 * l, true, 2, s));
+    // plain_ifft -> scale(1/l) -> swap_halves ride on the inverse transform, as in op_correlate
+    BDSP_TRY(fft_two_buffers<T>(m->v.data, m->v.buf, l, rows, true, BDSP_FFT_SHIFT_OUT, (T)1 / (T)l, -1, (T)0, &in_b, s));
+    if (in_b) m->v.trade();
+    return BDSP_OK; // delta is untouched
+}
+
 } // namespace
 
 // ==============================================================================================
@@ -2603,6 +2663,19 @@ BDSP_MAT(64, double, MatBuf64, VecBuf64)
 BDSP_MAT_STATS(32, float, MatBuf32, VecBuf32)
 BDSP_MAT_STATS(64, double, MatBuf64, VecBuf64)
 #undef BDSP_MAT_STATS
+
+// cross correlation of the rows (mat_prepare_argument / mat_correlate above)
+#define BDSP_MAT_CORR(SFX, T, MB, VB)                                                                       \
+    int32_t bdsp_hip_mat_prepare_argument##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_prepare_argument<T>(a, false)); } \
+    int32_t bdsp_hip_mat_prepare_argument_padded##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_prepare_argument<T>(a, true)); } \
+    int32_t bdsp_hip_mat_correlate##SFX(MB* m, const MB* other)                                             \
+    { DevMat<T>* a = M##SFX(m); const DevMat<T>* o = MC##SFX(other); return mat_code<T>(a, mat_correlate<T>(a, &o->v, o->rows, o->row_points(), o->row_points())); } \
+    int32_t bdsp_hip_mat_correlate_vector##SFX(MB* m, const VB* other)                                      \
+    { DevMat<T>* a = M##SFX(m); const DevVec<T>* o = H<T>(other); return mat_code<T>(a, mat_correlate<T>(a, o, a->rows, o->points(), 0)); }
+
+BDSP_MAT_CORR(32, float, MatBuf32, VecBuf32)
+BDSP_MAT_CORR(64, double, MatBuf64, VecBuf64)
+#undef BDSP_MAT_CORR
 
 // ---------------------------------------------------------------------------------------------- B3
 int bdsp_hip_dev_fft(int elem, void* data, void* scratch, size_t points, size_t batch, unsigned flags,

@@ -176,6 +176,20 @@ class DspMat:
         arr = (C.c_void_p * len(flat))(*[h._h for h in flat])
         return self._call("convolve_signal_mat", arr, len(flat))
 
+    def prepare_argument(self):
+        """Every row becomes the argument `correlate` takes: plain_fft, conjugated (CrossCorrelationArgumentOps)."""
+        return self._call("prepare_argument")
+
+    def prepare_argument_padded(self):
+        """As prepare_argument after Surround-padding every row to 2 * points - 1; 7 for rows of one point or less."""
+        return self._call("prepare_argument_padded")
+
+    def correlate(self, other):
+        """Cross-correlates row r with row r of a prepared DspMat, or every row with one prepared DspVec
+        (matrix/src/time_freq.rs:241-264).  Rows grow to the argument's points.  Codes: 5 (self not complex / time or
+        `other` not prepared; self is poisoned), 7 (argument not longer than the rows, or unequal row counts)."""
+        return self._binary("correlate", other)
+
     def interpolatef(self, function, interpolation_factor, delay, conv_len, rolloff=0.0):
         return self._call("interpolatef", int(function), rolloff, interpolation_factor, delay, int(conv_len))
 

@@ -724,6 +724,19 @@ int32_t bdsp_hip_mat_real_dot_product_vector32(const MatBuf32 *m, const VecBuf32
 int32_t bdsp_hip_mat_complex_dot_product_vector32(const MatBuf32 *m, const VecBuf32 *factor, bdsp_complex32 *out, size_t len);
 int32_t bdsp_hip_mat_real_dot_product_vector_prec32(const MatBuf32 *m, const VecBuf32 *factor, double *out, size_t len);   /* :225-241 */
 int32_t bdsp_hip_mat_complex_dot_product_vector_prec32(const MatBuf32 *m, const VecBuf32 *factor, bdsp_complex64 *out, size_t len);
+/* Cross correlation of the rows (matrix/src/time_freq.rs:208-264; correlation.rs:96-160 per row): every row behaves as
+ * the vector function of the same name on that row.  prepare_argument: plain_fft of all rows, conjugated (real rows
+ * become complex, delta <- points * delta; a frequency-domain matrix is poisoned, -1).  prepare_argument_padded: every
+ * row Surround-padded to 2p-1 points first; 7 for p <= 1, matrix untouched.  correlate: `m` complex / time and `other`
+ * complex / frequency, else `m` is poisoned and the code is 5; `other`'s row points L must exceed m's, else 7, and the
+ * row counts must agree, else 7 (m unchanged both times).  Afterwards every row holds L complex points in the time
+ * domain -- zero_pad(L, Surround), plain_fft, x other, plain_ifft, 1/L, swap_halves -- delta as before; `other` is
+ * not modified; zero rows: 0.  One launch for L a power of two in [16, 4096], else a number of launches that does not
+ * depend on the row count.  _vector: every row with ONE prepared vector (not in the reference: time_freq.rs:233-239). */
+int32_t bdsp_hip_mat_prepare_argument32(MatBuf32 *m);                      /* matrix/src/time_freq.rs:208-229 */
+int32_t bdsp_hip_mat_prepare_argument_padded32(MatBuf32 *m);
+int32_t bdsp_hip_mat_correlate32(MatBuf32 *m, const MatBuf32 *other);        /* :241-264, row r with row r of other */
+int32_t bdsp_hip_mat_correlate_vector32(MatBuf32 *m, const VecBuf32 *other); /* every row with one prepared vector */
 
 MatBuf64 *bdsp_hip_mat_new64(int32_t is_complex, int32_t domain, size_t rows, size_t row_len, double delta); /* row_len in scalars; zero filled */
 void bdsp_hip_mat_delete64(MatBuf64 *m);
@@ -798,6 +811,10 @@ int32_t bdsp_hip_mat_real_dot_product_vector64(const MatBuf64 *m, const VecBuf64
 int32_t bdsp_hip_mat_complex_dot_product_vector64(const MatBuf64 *m, const VecBuf64 *factor, bdsp_complex64 *out, size_t len);
 int32_t bdsp_hip_mat_real_dot_product_vector_prec64(const MatBuf64 *m, const VecBuf64 *factor, double *out, size_t len);   /* :225-241 */
 int32_t bdsp_hip_mat_complex_dot_product_vector_prec64(const MatBuf64 *m, const VecBuf64 *factor, bdsp_complex64 *out, size_t len);
+int32_t bdsp_hip_mat_prepare_argument64(MatBuf64 *m);                      /* matrix/src/time_freq.rs:208-229 */
+int32_t bdsp_hip_mat_prepare_argument_padded64(MatBuf64 *m);
+int32_t bdsp_hip_mat_correlate64(MatBuf64 *m, const MatBuf64 *other);        /* :241-264, row r with row r of other */
+int32_t bdsp_hip_mat_correlate_vector64(MatBuf64 *m, const VecBuf64 *other); /* every row with one prepared vector */
 
 /* ==========================================================================================
  * B3 -- kernels on caller-owned DEVICE memory.  `stream` is a hipStream_t passed as void*
