@@ -297,6 +297,11 @@ for _s, _t, _R in (("32", _F, VectorInteropResult32), ("64", _D, VectorInteropRe
         _proto(_m + _n + _s, C.c_int32, _P)
     for _n in ("correlate", "correlate_vector"):
         _proto(_m + _n + _s, C.c_int32, _P, _P)
+    # differences, running sums, wrap / unwrap of the rows
+    for _n in ("diff", "diff_with_start", "cum_sum"):
+        _proto(_m + _n + _s, C.c_int32, _P)
+    for _n in ("wrap", "unwrap"):
+        _proto(_m + _n + _s, C.c_int32, _P, _t)
 
 WINDOW_FN32 = C.CFUNCTYPE(_F, _P, _SZ, _SZ)
 WINDOW_FN64 = C.CFUNCTYPE(_D, _P, _SZ, _SZ)

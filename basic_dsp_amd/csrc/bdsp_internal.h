@@ -262,6 +262,15 @@ bool mc_fused_len(size_t l); // a power of two in [16, 4096]: mc_correlate_fused
 template <typename T>
 int mc_correlate_fused(const T* in, T* out, const T* arg, size_t arg_stride, size_t rows, size_t p, size_t l, hipStream_t s);
 
+// mat_scan.hip -- diff, cum_sum and unwrap of every row of a matrix; the launch counts do not depend on `rows`
+// `rows` rows of row_len scalars -> rows of row_len - step (diff) or row_len (with_start) scalars, dense, out of place
+template <typename T> int ms_diff(const T* in, T* out, size_t rows, size_t row_len, size_t step, bool with_start, hipStream_t s);
+// in-place prefix sums per row; `scratch`: ms_cum_sum_scratch bytes (0 for rows of at most one scan chunk)
+template <typename T> size_t ms_cum_sum_scratch(size_t rows, size_t row_points, bool is_complex);
+template <typename T> int ms_cum_sum(T* x, size_t rows, size_t row_points, bool is_complex, void* scratch, hipStream_t s);
+// in-place unwrap of every (real) row: one launch
+template <typename T> int ms_unwrap(T* x, size_t rows, size_t row_len, T divisor, hipStream_t s);
+
 // bluestein.hip
 template <typename T> int bs_chirp(T* c, size_t n, bool inverse, hipStream_t s);
 template <typename T> int bs_kernel(const T* c, T* b, size_t n, size_t m, hipStream_t s);

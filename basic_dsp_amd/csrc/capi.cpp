@@ -1895,6 +1895,40 @@ int mat_multiply_frequency_response(DevMat<T>* m, int fid, T rolloff, T ratio)
     return mat_each_row<T>(m, [&](T* row, size_t len) { return ew_freq_response<T>(row, len, c, fid, rolloff, ratio, false, lib_stream()); });
 }
 
+// diff / diff_with_start / cum_sum / wrap / unwrap of every row (mat_scan.hip): each row as the vector function of the
+// same name (op_diff, op_cum_sum, op_math(MATH_WRAP), op_unwrap above).  diff shortens every row by one point; rows
+// that are empty stay empty.
+template <typename T>
+int mat_diff(DevMat<T>* m, bool with_start)
+{
+    const size_t step = m->v.complex_ ? 2 : 1, rl = m->row_len();
+    if (m->rows == 0 || rl < step) return BDSP_OK;
+    const size_t n_out = with_start ? rl : rl - step;
+    BDSP_TRY(ms_diff<T>(m->v.data, m->v.buf, m->rows, rl, step, with_start, lib_stream()));
+    m->v.trade();
+    m->v.valid_len = m->rows * n_out;
+    return BDSP_OK;
+}
+
+template <typename T>
+int mat_cum_sum(DevMat<T>* m)
+{
+    const size_t p = m->row_points();
+    if (m->rows == 0 || p == 0) return BDSP_OK;
+    hipStream_t s = lib_stream();
+    WsBlock sc;
+    const size_t bytes = ms_cum_sum_scratch<T>(m->rows, p, m->v.complex_);
+    if (bytes) BDSP_TRY(sc.alloc(bytes, s));
+    return ms_cum_sum<T>(m->v.data, m->rows, p, m->v.complex_, sc.p, s);
+}
+
+template <typename T>
+int mat_unwrap(DevMat<T>* m, T divisor)
+{
+    if (m->v.complex_) { m->v.poison(); return BDSP_OK; } // assert_real!, real_ops.rs:222-233
+    return ms_unwrap<T>(m->v.data, m->rows, m->row_len(), divisor, lib_stream());
+}
+
 template <typename T>
 DevVec<T>* mat_get_row(const DevMat<T>* m, size_t row)
 {
@@ -2676,6 +2710,18 @@ BDSP_MAT_STATS(64, double, MatBuf64, VecBuf64)
 BDSP_MAT_CORR(32, float, MatBuf32, VecBuf32)
 BDSP_MAT_CORR(64, double, MatBuf64, VecBuf64)
 #undef BDSP_MAT_CORR
+
+// differences, running sums, phase wrapping of the rows (mat_diff / mat_cum_sum / mat_unwrap above)
+#define BDSP_MAT_SCAN(SFX, T, MB)                                                                           \
+    int32_t bdsp_hip_mat_diff##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_diff<T>(a, false)); } \
+    int32_t bdsp_hip_mat_diff_with_start##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_diff<T>(a, true)); } \
+    int32_t bdsp_hip_mat_cum_sum##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_cum_sum<T>(a)); } \
+    int32_t bdsp_hip_mat_wrap##SFX(MB* m, T divisor) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_math<T>(&a->v, MATH_WRAP, divisor, true)); } \
+    int32_t bdsp_hip_mat_unwrap##SFX(MB* m, T divisor) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_unwrap<T>(a, divisor)); }
+
+BDSP_MAT_SCAN(32, float, MatBuf32)
+BDSP_MAT_SCAN(64, double, MatBuf64)
+#undef BDSP_MAT_SCAN
 
 // ---------------------------------------------------------------------------------------------- B3
 int bdsp_hip_dev_fft(int elem, void* data, void* scratch, size_t points, size_t batch, unsigned flags,

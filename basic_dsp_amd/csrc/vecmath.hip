@@ -9,6 +9,7 @@
 // from the reference is only the last-ulp behaviour of the math library underneath.
 #include "bdsp_internal.h"
 #include "ew_map.h"
+#include "scan_common.h"
 
 namespace bdsp {
 
@@ -230,8 +231,7 @@ template <typename T> int vm_diff(const T* in, T* out, size_t n_out, size_t step
 // ---- cum_sum: chunk sums -> scan of the chunk sums -> rescan of every chunk with its offset ---------------------
 // The running sum is carried in double whatever T is (the reference adds sequentially in T; the result here is the
 // correctly rounded-once prefix, compared with tolerance).  E interleaved sequences (1 real, 2 complex).
-constexpr int SCAN_PER_THREAD = 16;
-constexpr int SCAN_CHUNK = 256 * SCAN_PER_THREAD; // elements per workgroup
+// (SCAN_PER_THREAD, SCAN_CHUNK: scan_common.h, shared with the per-row scans of mat_scan.hip)
 
 // chunk sums: order does not matter, so the chunk is read with unit stride across the workgroup
 template <typename T, int E>
@@ -357,21 +357,7 @@ template <typename T> int vm_cum_sum(T* x, size_t len, bool is_complex, void* sc
 // y[j] = F(x[j], y[j-1]) with a data-dependent branch on the ALREADY UNWRAPPED neighbour: a genuinely sequential
 // recurrence (its state does not reduce to an associative operator), so one lane walks the vector while the
 // wavefront stages tiles through LDS with coalesced packets.  Exact, not fast (see DESIGN.md for the rate).
-// fmod on the serial critical path: the remainder a - trunc(a/b)*b is exactly representable, so one fma returns it
-// exactly when the quotient is right; a quotient off by one (a/b rounded across an integer) shows as a remainder
-// outside [0, |b|) and is redone.  Huge quotients, infinities and NaNs go to the library function.
-template <typename T>
-__device__ __forceinline__ T fmod_exact(T a, T b, T inv_abs_b)
-{
-    const T A = fabs(a), Bv = fabs(b);
-    T q = trunc(A * inv_abs_b); // a guess within one of trunc(A / Bv): the checks below settle it
-    if (!(q < (T)(sizeof(T) == 4 ? 4194304.0 : 2251799813685248.0))) return fmod(a, b);
-    T r = fma(-q, Bv, A);
-    if (r < T(0)) r = fma(-(q - T(1)), Bv, A);
-    else if (r >= Bv) r = fma(-(q + T(1)), Bv, A);
-    return copysign(r, a);
-}
-
+// fmod_exact, the remainder on the serial critical path: scan_common.h (mat_scan.hip compiles the same function).
 template <typename T>
 __global__ __launch_bounds__(64) void k_unwrap(T* __restrict__ x, size_t len, T divisor)
 {

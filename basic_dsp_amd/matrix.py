@@ -129,6 +129,29 @@ class DspMat:
     def phase(self):
         return self._call("phase")
 
+    # ------------------------------------------------------------------ differences, running sums, phase wrapping
+    # Every row as the DspVec method of the same name on that row; one batched launch (cum_sum: three for rows of
+    # more than 4096 points) whatever the number of rows.
+    def diff(self):
+        """Every row loses its first point: row[j] = row[j + 1] - row[j]."""
+        return self._call("diff")
+
+    def diff_with_start(self):
+        """As diff, but every row keeps its first point."""
+        return self._call("diff_with_start")
+
+    def cum_sum(self):
+        """Running sum of every row (carried in double, rounded once per element, as DspVec.cum_sum)."""
+        return self._call("cum_sum")
+
+    def wrap(self, divisor):
+        """fmod(x, divisor) of every element; a complex matrix is poisoned (-1)."""
+        return self._call("wrap", divisor)
+
+    def unwrap(self, divisor):
+        """Undoes wrap along every row (divisor 2 pi for a phase); a complex matrix is poisoned (-1)."""
+        return self._call("unwrap", divisor)
+
     # ------------------------------------------------------------------ transforms, windows, index moves
     def plain_fft(self):
         return self._call("plain_fft")

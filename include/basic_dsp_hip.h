@@ -737,6 +737,18 @@ int32_t bdsp_hip_mat_prepare_argument32(MatBuf32 *m);                      /* ma
 int32_t bdsp_hip_mat_prepare_argument_padded32(MatBuf32 *m);
 int32_t bdsp_hip_mat_correlate32(MatBuf32 *m, const MatBuf32 *other);        /* :241-264, row r with row r of other */
 int32_t bdsp_hip_mat_correlate_vector32(MatBuf32 *m, const VecBuf32 *other); /* every row with one prepared vector */
+/* Differences, running sums and phase wrapping of the rows (matrix/src/general/elementary.rs:206-225 DiffSumOps,
+ * matrix/src/real.rs:69-83 ModuloOps): every row behaves as the vector function OF THE SAME NAME on that row.  (The
+ * reference's matrix diff_with_start and cum_sum both forward to v.diff(), elementary.rs:214-224 -- a slip there, not
+ * reproduced here.)  diff shortens every row by one point, rows that are empty stay empty; cum_sum carries the running
+ * sum in double and rounds once per element, as cum_sum32/64; wrap / unwrap on a complex matrix poison it, -1, with no
+ * launch (real_ops.rs:222-233).  Zero rows or empty rows: 0, no launch; -1 for a poisoned matrix.  Domain, delta and
+ * number space stay.  One launch each (cum_sum: three for rows of more than 4096 points), whatever the row count. */
+int32_t bdsp_hip_mat_diff32(MatBuf32 *m);
+int32_t bdsp_hip_mat_diff_with_start32(MatBuf32 *m);
+int32_t bdsp_hip_mat_cum_sum32(MatBuf32 *m);
+int32_t bdsp_hip_mat_wrap32(MatBuf32 *m, float divisor);
+int32_t bdsp_hip_mat_unwrap32(MatBuf32 *m, float divisor);
 
 MatBuf64 *bdsp_hip_mat_new64(int32_t is_complex, int32_t domain, size_t rows, size_t row_len, double delta); /* row_len in scalars; zero filled */
 void bdsp_hip_mat_delete64(MatBuf64 *m);
@@ -815,6 +827,12 @@ int32_t bdsp_hip_mat_prepare_argument64(MatBuf64 *m);                      /* ma
 int32_t bdsp_hip_mat_prepare_argument_padded64(MatBuf64 *m);
 int32_t bdsp_hip_mat_correlate64(MatBuf64 *m, const MatBuf64 *other);        /* :241-264, row r with row r of other */
 int32_t bdsp_hip_mat_correlate_vector64(MatBuf64 *m, const VecBuf64 *other); /* every row with one prepared vector */
+/* differences, running sums, wrap / unwrap of the rows: as the f32 set above */
+int32_t bdsp_hip_mat_diff64(MatBuf64 *m);
+int32_t bdsp_hip_mat_diff_with_start64(MatBuf64 *m);
+int32_t bdsp_hip_mat_cum_sum64(MatBuf64 *m);
+int32_t bdsp_hip_mat_wrap64(MatBuf64 *m, double divisor);
+int32_t bdsp_hip_mat_unwrap64(MatBuf64 *m, double divisor);
 
 /* ==========================================================================================
  * B3 -- kernels on caller-owned DEVICE memory.  `stream` is a hipStream_t passed as void*
