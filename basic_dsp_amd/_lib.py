@@ -302,6 +302,11 @@ for _s, _t, _R in (("32", _F, VectorInteropResult32), ("64", _D, VectorInteropRe
         _proto(_m + _n + _s, C.c_int32, _P)
     for _n in ("wrap", "unwrap"):
         _proto(_m + _n + _s, C.c_int32, _P, _t)
+    # FFT-domain resampling and decimation of the rows
+    _proto(_m + "interpolatei" + _s, C.c_int32, _P, C.c_int32, _t, C.c_int32)
+    _proto(_m + "interpolate" + _s, C.c_int32, _P, C.c_int32, _t, _SZ, _t)
+    _proto(_m + "interpft" + _s, C.c_int32, _P, _SZ)
+    _proto(_m + "decimatei" + _s, C.c_int32, _P, C.c_uint32, C.c_uint32)
 
 WINDOW_FN32 = C.CFUNCTYPE(_F, _P, _SZ, _SZ)
 WINDOW_FN64 = C.CFUNCTYPE(_D, _P, _SZ, _SZ)

@@ -271,6 +271,27 @@ template <typename T> int ms_cum_sum(T* x, size_t rows, size_t row_points, bool 
 // in-place unwrap of every (real) row: one launch
 template <typename T> int ms_unwrap(T* x, size_t rows, size_t row_len, T divisor, hipStream_t s);
 
+// mat_resample.hip -- FFT-domain resampling and decimation of every row of a matrix; the launch counts do not depend on
+// `rows`
+// ew_spectrum_resample for `rows` spectra at once (src_points complex apart in `in`, dst_points apart in `out`), plus
+// mode 2 = the crop of interpolate_downsample; mode 1 with dst_points == src_points applies a pure delay; one launch
+template <typename T>
+int rs_spectrum_rows(const T* in, T* out, size_t rows, size_t src_points, size_t dst_points, int mode, int fid, T rolloff,
+                     T ratio, double phase_inc, hipStream_t s);
+// rg_decimate for `rows` rows of `points` elements (elem scalars each) -> out_points elements; one launch
+template <typename T>
+int rs_decimate_rows(const T* in, T* out, size_t rows, size_t points, size_t out_points, size_t elem, size_t factor,
+                     size_t delay, hipStream_t s);
+// new_points = f * points with f >= 2 an integer and new_points a power of two in [16, 4096]: rs_fused applies
+bool rs_fused_applies(size_t points, size_t new_points);
+// rows x points (real scalars if is_real, else complex) -> rows x new_points of the same number space: zero interleave,
+// transform, x the multiplier ew_spectrum_resample applies per destination bin (mode 0: interpolatei; mode 1:
+// interpolate / interpft with fid, ratio and phase_inc as there), inverse transform, 1/new_points -- one launch; in and
+// out must not overlap
+template <typename T>
+int rs_fused(const T* in, T* out, size_t rows, size_t points, size_t new_points, bool is_real, int mode, int fid,
+             T rolloff, T ratio, double phase_inc, hipStream_t s);
+
 // bluestein.hip
 template <typename T> int bs_chirp(T* c, size_t n, bool inverse, hipStream_t s);
 template <typename T> int bs_kernel(const T* c, T* b, size_t n, size_t m, hipStream_t s);

@@ -2089,6 +2089,97 @@ int mat_correlate(DevMat<T>* m, const DevVec<T>* o, size_t o_rows, size_t l, siz
     return BDSP_OK; // delta is untouched
 }
 
+// FFT-domain resampling and decimation of the rows (matrix/src/time_freq.rs:266-327 forwards InterpolationOps row by row):
+// every row behaves as op_interpolatei / op_interpolate / op_decimatei would on it, with launch counts that do not depend
+// on the row count.  Integer factors into a power of two of at most 4096 points take one launch (rs_fused); everything
+// else is batched forward transform -> rs_spectrum_rows -> batched inverse transform on the two buffers, both reserved
+// for rows * 2 * max(points, new points) scalars before the first launch.
+template <typename T>
+int mat_resample_general(DevMat<T>* m, size_t points, size_t np, bool spectrum, int mode, int fid, T rolloff, T ratio,
+                         double phase_inc)
+{
+    hipStream_t s = lib_stream();
+    const bool was_complex = m->v.complex_;
+    const size_t rows = m->rows;
+    BDSP_TRY(m->v.reserve(rows * 2 * (points > np ? points : np)));
+    bool in_b = false;
+    BDSP_TRY(fft_two_buffers<T>(m->v.data, m->v.buf, points, rows, false, was_complex ? 0u : FFT_IN_REAL, (T)1, -1, (T)0, &in_b, s));
+    if (in_b) m->v.trade();
+    if (spectrum) {
+        BDSP_TRY(rs_spectrum_rows<T>(m->v.data, m->v.buf, rows, points, np, mode, fid, rolloff, ratio, phase_inc, s));
+        m->v.trade();
+    }
+    // plain_ifft then scale(1/points): the scale rides on the inverse transform's input; real rows keep the real parts
+    BDSP_TRY(fft_two_buffers<T>(m->v.data, m->v.buf, np, rows, true, was_complex ? 0u : FFT_OUT_REAL, (T)1 / (T)np, -1, (T)0, &in_b, s));
+    if (in_b) m->v.trade();
+    m->v.valid_len = rows * np * (was_complex ? 2 : 1);
+    return BDSP_OK;
+}
+
+template <typename T>
+int mat_resample_fused(DevMat<T>* m, size_t points, size_t np, int mode, int fid, T rolloff, T ratio, double phase_inc)
+{
+    const size_t step = m->v.complex_ ? 2 : 1;
+    BDSP_TRY(m->v.reserve(m->rows * np * step));
+    BDSP_TRY(rs_fused<T>(m->v.data, m->v.buf, m->rows, points, np, !m->v.complex_, mode, fid, rolloff, ratio, phase_inc, lib_stream()));
+    m->v.trade();
+    m->v.valid_len = m->rows * np * step;
+    return BDSP_OK;
+}
+
+template <typename T>
+int mat_interpolatei(DevMat<T>* m, int fid, T rolloff, int factor)
+{
+    if (factor <= 1) return BDSP_OK;
+    const size_t points = m->row_points(), np = points * (size_t)factor;
+    if (m->rows == 0 || points == 0) return BDSP_OK;
+    if (rs_fused_applies(points, np)) return mat_resample_fused<T>(m, points, np, 0, fid, rolloff, (T)factor, 0.0);
+    return mat_resample_general<T>(m, points, np, true, 0, fid, rolloff, (T)factor, 0.0);
+    // delta stays, as in op_interpolatei
+}
+
+// fid < 0 = no frequency response (interpft)
+template <typename T>
+int mat_interpolate(DevMat<T>* m, int fid, T rolloff, size_t dest_points, T delay)
+{
+    if (dest_points == 0) return BDSP_ERR_ARG_LENGTH;
+    if (m->rows == 0) return BDSP_OK;
+    const size_t points = m->row_points();
+    if (points == 0) return BDSP_ERR_ARG_LENGTH;
+    const T delta_t = m->v.delta;
+    const T factorf = (T)dest_points / (T)points;
+    // as op_interpolate computes them (ew_linear_phase's phase_inc in T, then widened)
+    const T dly = delay / delta_t;
+    const T phase_inc_t = (T)2 * (T)3.14159265358979323846 * dly / (T)points;
+    const double phase_inc = delay != (T)0 ? (double)phase_inc_t : 0.0;
+    if (rs_fused_applies(points, dest_points))
+        BDSP_TRY(mat_resample_fused<T>(m, points, dest_points, 1, fid < 0 ? -1 : fid, rolloff, factorf, phase_inc));
+    else if (dest_points > points)
+        BDSP_TRY(mat_resample_general<T>(m, points, dest_points, true, 1, fid < 0 ? -1 : fid, rolloff, factorf, phase_inc));
+    else if (dest_points < points) // interpolate_downsample: the crop and the scale, no response
+        BDSP_TRY(mat_resample_general<T>(m, points, dest_points, true, 2, -1, (T)0, (T)(2 * dest_points) / (T)(2 * points), phase_inc));
+    else // equal lengths: a pure delay (mode 1 moves no bin), or the two transforms alone
+        BDSP_TRY(mat_resample_general<T>(m, points, dest_points, delay != (T)0, 1, -2, (T)0, (T)1, phase_inc));
+    m->v.delta = delta_t / factorf;
+    return BDSP_OK;
+}
+
+template <typename T>
+int mat_decimatei(DevMat<T>* m, unsigned factor, unsigned delay)
+{
+    if (factor == 0) return BDSP_ERR_ARG_LENGTH;
+    const size_t rows = m->rows, elem = m->v.complex_ ? 2 : 1, points = m->row_points();
+    if (rows == 0) return BDSP_OK;
+    const size_t outp = delay < points ? (points - delay + factor - 1) / factor : 0;
+    if (outp) {
+        BDSP_TRY(m->v.reserve(rows * outp * elem));
+        BDSP_TRY(rs_decimate_rows<T>(m->v.data, m->v.buf, rows, points, outp, elem, factor, delay, lib_stream()));
+        m->v.trade();
+    }
+    m->v.valid_len = rows * outp * elem;
+    return BDSP_OK;
+}
+
 } // namespace
 
 // ==============================================================================================
@@ -2722,6 +2813,21 @@ BDSP_MAT_CORR(64, double, MatBuf64, VecBuf64)
 BDSP_MAT_SCAN(32, float, MatBuf32)
 BDSP_MAT_SCAN(64, double, MatBuf64)
 #undef BDSP_MAT_SCAN
+
+// FFT-domain resampling and decimation of the rows (mat_interpolatei / mat_interpolate / mat_decimatei above)
+#define BDSP_MAT_RESAMPLE(SFX, T, MB)                                                                       \
+    int32_t bdsp_hip_mat_interpolatei##SFX(MB* m, int32_t frequency_response, T rolloff, int32_t interpolation_factor) \
+    { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_interpolatei<T>(a, frequency_response == 0 ? 0 : 1, rolloff, interpolation_factor)); } \
+    int32_t bdsp_hip_mat_interpolate##SFX(MB* m, int32_t frequency_response, T rolloff, size_t dest_points, T delay) \
+    { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_interpolate<T>(a, frequency_response == 0 ? 0 : 1, rolloff, dest_points, delay)); } \
+    int32_t bdsp_hip_mat_interpft##SFX(MB* m, size_t dest_points)                                           \
+    { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_interpolate<T>(a, -1, (T)0, dest_points, (T)0)); } \
+    int32_t bdsp_hip_mat_decimatei##SFX(MB* m, uint32_t decimation_factor, uint32_t delay)                  \
+    { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_decimatei<T>(a, decimation_factor, delay)); }
+
+BDSP_MAT_RESAMPLE(32, float, MatBuf32)
+BDSP_MAT_RESAMPLE(64, double, MatBuf64)
+#undef BDSP_MAT_RESAMPLE
 
 // ---------------------------------------------------------------------------------------------- B3
 int bdsp_hip_dev_fft(int elem, void* data, void* scratch, size_t points, size_t batch, unsigned flags,

@@ -219,6 +219,32 @@ class DspMat:
     def multiply_frequency_response(self, function, ratio, rolloff=0.0):
         return self._call("multiply_frequency_response", int(function), rolloff, ratio)
 
+    # ------------------------------------------------------------------ FFT-domain resampling, decimation
+    # Every row as the DspVec method of the same name on that row; real rows stay real.  One launch when the new row
+    # length is an integer multiple of the old one and a power of two of at most 4096 points, else a batched forward
+    # transform, one spectrum pass and a batched inverse transform -- whatever the number of rows.
+    def interpolatei(self, function, interpolation_factor, rolloff=0.0):
+        """Every row grows to points * interpolation_factor: zero interleave, then `function` (CONV_SINC or
+        CONV_RAISED_COSINE with `rolloff`) as a low pass in the frequency domain.  delta stays.  A factor <= 1 leaves the
+        matrix as it is (0)."""
+        return self._call("interpolatei", int(function), rolloff, int(interpolation_factor))
+
+    def interpolate(self, function, dest_points, delay=0.0, rolloff=0.0):
+        """Every row resampled to dest_points (more or fewer than before) through its spectrum, shifted by `delay` (in
+        units of delta); function=None is interpft.  delta <- delta / (dest_points / points).  7 for dest_points == 0
+        or rows without points."""
+        if function is None:
+            return self._call("interpft", int(dest_points))
+        return self._call("interpolate", int(function), rolloff, int(dest_points), delay)
+
+    def interpft(self, dest_points):
+        """Every row resampled to dest_points by padding or cropping its spectrum (no response, no delay)."""
+        return self._call("interpft", int(dest_points))
+
+    def decimatei(self, decimation_factor, delay):
+        """Every row keeps the points delay, delay + decimation_factor, ...; 7 for a factor of 0.  delta stays."""
+        return self._call("decimatei", int(decimation_factor), int(delay))
+
     # ------------------------------------------------------------------ per-row statistics, sums, dot products
     # One batched device pass each (matrix/src/general/statistics.rs, mod.rs); results per row as numpy columns.
     _STAT_KEYS = ("sum", "count", "average", "rms", "min", "min_index", "max", "max_index")

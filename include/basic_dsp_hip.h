@@ -749,6 +749,28 @@ int32_t bdsp_hip_mat_diff_with_start32(MatBuf32 *m);
 int32_t bdsp_hip_mat_cum_sum32(MatBuf32 *m);
 int32_t bdsp_hip_mat_wrap32(MatBuf32 *m, float divisor);
 int32_t bdsp_hip_mat_unwrap32(MatBuf32 *m, float divisor);
+/* FFT-domain resampling and decimation of the rows (matrix/src/time_freq.rs:266-327 InterpolationOps; interpolation.rs:
+ * 484-633 per row): every row behaves as the vector function OF THE SAME NAME on that row, and the arguments are the
+ * vector facade's (frequency_response 0 = sinc, anything else = raised cosine(rolloff)).  Real rows stay real, complex
+ * rows complex; every row gets the same new length: points * interpolation_factor, dest_points, or
+ * ceil((points - delay) / decimation_factor) (0 for delay >= points).  interpolate / interpft set
+ * delta <- delta / (dest_points / points), computed in the matrix's precision; interpolatei and decimatei leave delta
+ * alone; domain and number space are neither checked nor changed, as in the vector functions.  Codes: interpolatei with
+ * a factor <= 1: 0, matrix untouched; interpolate / interpft with dest_points == 0 or rows of zero points: 7, matrix
+ * untouched; decimatei with factor 0: 7; zero rows: 0, no launch; -1 for a poisoned matrix.
+ * Launches, whatever the row count: ONE when the new length is an integer multiple (>= 2) of the row length and a power
+ * of two in [16, 4096] (the row is read once and written once); otherwise batched forward transform -> one spectrum
+ * pass over all rows -> batched inverse transform, as many launches as those transforms take for ONE row length
+ * (three for power-of-two lengths up to 4096; interpolate to the same length with delay 0 skips the spectrum pass).
+ * decimatei: one launch.  Memory: the general path grows both device buffers of the matrix to
+ * rows * 2 * max(points, new points) scalars before its first launch (real rows too: their spectra are complex); the
+ * one-launch path and decimatei to rows * new row length.  Custom (callback) responses are not offered for matrices. */
+int32_t bdsp_hip_mat_interpolatei32(MatBuf32 *m, int32_t frequency_response, float rolloff,
+                                    int32_t interpolation_factor);            /* matrix/src/time_freq.rs:282-293 */
+int32_t bdsp_hip_mat_interpolate32(MatBuf32 *m, int32_t frequency_response, float rolloff,
+                                   size_t dest_points, float delay);          /* :295-307 */
+int32_t bdsp_hip_mat_interpft32(MatBuf32 *m, size_t dest_points);             /* :309-317 */
+int32_t bdsp_hip_mat_decimatei32(MatBuf32 *m, uint32_t decimation_factor, uint32_t delay); /* :319-326 */
 
 MatBuf64 *bdsp_hip_mat_new64(int32_t is_complex, int32_t domain, size_t rows, size_t row_len, double delta); /* row_len in scalars; zero filled */
 void bdsp_hip_mat_delete64(MatBuf64 *m);
@@ -833,6 +855,13 @@ int32_t bdsp_hip_mat_diff_with_start64(MatBuf64 *m);
 int32_t bdsp_hip_mat_cum_sum64(MatBuf64 *m);
 int32_t bdsp_hip_mat_wrap64(MatBuf64 *m, double divisor);
 int32_t bdsp_hip_mat_unwrap64(MatBuf64 *m, double divisor);
+/* FFT-domain resampling and decimation of the rows: as the f32 set above */
+int32_t bdsp_hip_mat_interpolatei64(MatBuf64 *m, int32_t frequency_response, double rolloff,
+                                    int32_t interpolation_factor);
+int32_t bdsp_hip_mat_interpolate64(MatBuf64 *m, int32_t frequency_response, double rolloff,
+                                   size_t dest_points, double delay);
+int32_t bdsp_hip_mat_interpft64(MatBuf64 *m, size_t dest_points);
+int32_t bdsp_hip_mat_decimatei64(MatBuf64 *m, uint32_t decimation_factor, uint32_t delay);
 
 /* ==========================================================================================
  * B3 -- kernels on caller-owned DEVICE memory.  `stream` is a hipStream_t passed as void*
