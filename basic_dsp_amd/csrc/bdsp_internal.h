@@ -167,8 +167,10 @@ template <typename T> int ew_conj(T* x, size_t len, hipStream_t s);
 template <typename T> int ew_mul_cexp(T* x, size_t len, T a, T b, hipStream_t s);
 template <typename T> int ew_complex_to_real(const T* x, T* out, size_t len, int kind, hipStream_t s);
 template <typename T> int ew_window(T* x, size_t len, bool is_complex, int id, T alpha, bool unapply, hipStream_t s);
+template <typename T> int ew_window_rows(T* x, size_t rows, size_t row_len, bool is_complex, int id, T alpha, bool unapply, hipStream_t s);
 template <typename T> int ew_fill(T* x, size_t len, T value, hipStream_t s);
 template <typename T> int ew_freq_response(T* x, size_t len, bool is_complex, int fid, T rolloff, T ratio, bool shifted, hipStream_t s);
+template <typename T> int ew_freq_response_rows(T* x, size_t rows, size_t row_len, bool is_complex, int fid, T rolloff, T ratio, bool shifted, hipStream_t s);
 template <typename T> int ew_linear_phase(T* x, size_t len, T delay, hipStream_t s);
 // spectrum of N points -> dst_points, out of place, one trip (mode 0: periodic repetition = the transform of the
 // zero-interleaved vector; mode 1: zero_pad(Center) with the linear phase on the source bin), x the frequency response

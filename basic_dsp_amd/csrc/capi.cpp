@@ -853,6 +853,7 @@ int op_fft(DevVec<T>* v, bool inverse, bool shift, int window /* -1 none */, siz
     } else {
         if (!v->freq) { v->poison(); v->complex_ = true; v->freq = true; return BDSP_OK; } // :142-147
     }
+    if (rows == 0) { v->valid_len = 0; v->complex_ = true; v->freq = !inverse; return BDSP_OK; } // a matrix without rows
     unsigned flags = 0;
     size_t points = v->points() / rows;
     if (!v->complex_) { // real input is zero-interleaved to complex first (:147-150)
@@ -1720,10 +1721,12 @@ int dot(const DevVec<T>* v, const DevVec<T>* o, bool cplx, double* re, double* i
 }
 
 // ----------------------------------------------------------------------------------------------
-// Matrix / batch API: `rows` equally long vectors back to back in ONE allocation, every operation a
-// batched launch over all rows.  Mirrors the matrix crate (matrix/src/lib.rs:195-208 applies an
-// operation to the rows one after the other; matrix/src/time_freq.rs:49-530 forwards the
-// time/frequency traits row by row) -- here the row loop is the grid's batch dimension.
+// Matrix / batch API: `rows` equally long vectors back to back in ONE allocation; a row may start at any
+// scalar, so nothing here may assume a 16-byte aligned row.  Operations are batched launches over all rows
+// except the ones that go through mat_resize_rows and the MIMO convolution (one launch per row).  Mirrors
+// the matrix crate (matrix/src/lib.rs:195-208 applies an operation to the rows one after the other;
+// matrix/src/time_freq.rs:49-530 forwards the time/frequency traits row by row) -- here the row loop is
+// the grid's batch dimension.
 // ----------------------------------------------------------------------------------------------
 template <typename T>
 struct DevMat {
@@ -1754,15 +1757,6 @@ template <typename T> int mat_code(DevMat<T>* m, int code)
 {
     if (code == BDSP_OK && m->v.erroneous()) return BDSP_ERR_POISONED;
     return code;
-}
-
-// run a single-vector kernel launcher on every row (index-dependent maps): fn(row_ptr, row_len)
-template <typename T, class F>
-int mat_each_row(DevMat<T>* m, F fn)
-{
-    const size_t rl = m->row_len();
-    for (size_t r = 0; r < m->rows; ++r) BDSP_TRY(fn(m->v.data + r * rl, rl));
-    return BDSP_OK;
 }
 
 // rows change length: fn(in_row, out_row) writes new_len scalars per row into the trade buffer
@@ -1803,8 +1797,8 @@ int mat_window(DevMat<T>* m, int window, bool unapply)
     int wid;
     T alpha;
     map_window<T>(window, &wid, &alpha);
-    const bool c = m->v.complex_;
-    return mat_each_row<T>(m, [&](T* row, size_t len) { return ew_window<T>(row, len, c, wid, alpha, unapply, lib_stream()); });
+    // one launch over the flat allocation: the window value depends on the position in the row alone
+    return ew_window_rows<T>(m->v.data, m->rows, m->row_len(), m->v.complex_, wid, alpha, unapply, lib_stream());
 }
 
 template <typename T>
@@ -1820,7 +1814,8 @@ template <typename T>
 int mat_zero_pad(DevMat<T>* m, size_t points, int option)
 {
     const size_t step = m->v.complex_ ? 2 : 1, len = points * step, rl = m->row_len();
-    if (len <= rl) return BDSP_ERR_ARG_LENGTH;
+    if (len <= rl) return BDSP_ERR_ARG_LENGTH; // an argument error comes first, as in every other call
+    if (m->v.erroneous()) return BDSP_OK; // a poisoned matrix stays poisoned: padding its empty rows would hide the error
     const int opt = option == 0 ? 0 : (option == 1 ? 1 : 2);
     const bool c = m->v.complex_;
     return mat_resize_rows<T>(m, len, [&](const T* in, T* out) { return rg_zero_pad<T>(in, out, rl, c, points, opt, lib_stream()); });
@@ -1891,8 +1886,7 @@ template <typename T>
 int mat_multiply_frequency_response(DevMat<T>* m, int fid, T rolloff, T ratio)
 {
     if (!m->v.freq) { m->v.poison(); return BDSP_OK; }
-    const bool c = m->v.complex_;
-    return mat_each_row<T>(m, [&](T* row, size_t len) { return ew_freq_response<T>(row, len, c, fid, rolloff, ratio, false, lib_stream()); });
+    return ew_freq_response_rows<T>(m->v.data, m->rows, m->row_len(), m->v.complex_, fid, rolloff, ratio, false, lib_stream());
 }
 
 // diff / diff_with_start / cum_sum / wrap / unwrap of every row (mat_scan.hip): each row as the vector function of the
@@ -2682,7 +2676,7 @@ BDSP_STATS(64, double, VecBuf64)
     int32_t bdsp_hip_mat_upload##SFX(MB* m, const T* data, size_t len) { return mat_transfer<T>(M##SFX(m), nullptr, data, len); } \
     int32_t bdsp_hip_mat_download##SFX(MB* m, T* out, size_t len) { return mat_transfer<T>(M##SFX(m), out, nullptr, len); } \
     VB* bdsp_hip_mat_get_row##SFX(const MB* m, size_t row) { return reinterpret_cast<VB*>(mat_get_row<T>(MC##SFX(m), row)); } \
-    int32_t bdsp_hip_mat_set_row##SFX(MB* m, size_t row, const VB* vector) { return mat_set_row<T>(M##SFX(m), row, H<T>(vector)); } \
+    int32_t bdsp_hip_mat_set_row##SFX(MB* m, size_t row, const VB* vector) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_set_row<T>(a, row, H<T>(vector))); } \
     int32_t bdsp_hip_mat_real_scale##SFX(MB* m, T f) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, ew_real_scale<T>(a->v.data, a->v.valid_len, f, lib_stream())); } \
     int32_t bdsp_hip_mat_real_offset##SFX(MB* m, T f) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, ew_real_offset<T>(a->v.data, a->v.valid_len, a->v.complex_, f, lib_stream())); } \
     int32_t bdsp_hip_mat_complex_scale##SFX(MB* m, T re, T im)                                              \

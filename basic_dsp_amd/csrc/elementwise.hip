@@ -72,39 +72,48 @@ template <typename T> struct OpMulCexp {
         }
     }
 };
-template <typename T> struct OpWindow {
-    struct Params { int id; T alpha; size_t points; int is_complex; int unapply; };
+// ROWS: x holds equally long rows back to back (the matrix API, one launch over the flat allocation): the position is
+// the scalar index modulo row_len, carried along the packet, which may straddle two rows.  A complex row has an even
+// scalar length, so a pair never straddles.  The arithmetic per element is the vector path's, bit for bit.
+template <typename T, bool ROWS = false> struct OpWindow {
+    struct Params { int id; T alpha; size_t points; int is_complex; int unapply; size_t row_len; };
     static __device__ __forceinline__ void apply(T* e, int n, size_t i0, Params p)
     {
         // time.rs:32-66 -> vector_types/mod.rs:526-597
+        size_t q = ROWS ? i0 % p.row_len : i0;
         if (p.is_complex) {
             for (int i = 0; i + 1 < n; i += 2) {
-                T w = window_value_sym<T>(p.id, p.alpha, (i0 + i) / 2, p.points);
+                T w = window_value_sym<T>(p.id, p.alpha, q / 2, p.points);
                 if (p.unapply) w = (T)1 / w;
                 T re = e[i], im = e[i + 1];
                 e[i] = re * w - im * (T)0; // Complex * Complex::new(w, 0)
                 e[i + 1] = re * (T)0 + im * w;
+                q += 2;
+                if (ROWS && q >= p.row_len) q = 0;
             }
         } else {
             for (int i = 0; i < n; ++i) {
-                T w = window_value_sym<T>(p.id, p.alpha, i0 + i, p.points);
+                T w = window_value_sym<T>(p.id, p.alpha, q, p.points);
                 if (p.unapply) w = (T)1 / w;
                 e[i] = e[i] * w;
+                ++q;
+                if (ROWS && q >= p.row_len) q = 0;
             }
         }
     }
 };
 // multiply_function_priv, symmetric functions (time_freq/mod.rs:655-721): element i takes the value
-// of the function on the negative half of the axis, j = -|i - center|.
-template <typename T> struct OpFreqResp {
-    struct Params { int id; T rolloff; T ratio; size_t points; int is_complex; int shifted; };
+// of the function on the negative half of the axis, j = -|i - center|.  ROWS as in OpWindow.
+template <typename T, bool ROWS = false> struct OpFreqResp {
+    struct Params { int id; T rolloff; T ratio; size_t points; int is_complex; int shifted; size_t row_len; };
     static __device__ __forceinline__ void apply(T* e, int n, size_t i0, Params p)
     {
         const size_t offset = p.points % 2;
         const T maxv = (T)(p.points - offset) / (T)2;
         const int step = p.is_complex ? 2 : 1;
+        size_t q = ROWS ? i0 % p.row_len : i0;
         for (int i = 0; i + step - 1 < n; i += step) {
-            T j = -maxv + (T)((i0 + i) / step);
+            T j = -maxv + (T)(q / step);
             if (j > (T)0) j = -j;
             T arg = p.ratio * conv_freq_value<T>(p.id, p.rolloff, fft_swap_x<T>(p.shifted != 0, j, maxv) * p.ratio);
             if (p.is_complex) {
@@ -112,6 +121,8 @@ template <typename T> struct OpFreqResp {
                 e[i] = re * arg - im * (T)0;
                 e[i + 1] = re * (T)0 + im * arg;
             } else e[i] = e[i] * arg;
+            q += step;
+            if (ROWS && q >= p.row_len) q = 0;
         }
     }
 };
@@ -160,14 +171,27 @@ template <typename T> int ew_mul_cexp(T* x, size_t len, T a, T b, hipStream_t s)
 template <typename T> int ew_window(T* x, size_t len, bool is_complex, int id, T alpha, bool unapply, hipStream_t s)
 {
     size_t points = is_complex ? len / 2 : len;
-    return launch_map<T, OpWindow<T>>(x, len, {id, alpha, points, (int)is_complex, (int)unapply}, s);
+    return launch_map<T, OpWindow<T>>(x, len, {id, alpha, points, (int)is_complex, (int)unapply, len}, s);
+}
+// every row of `rows` rows of row_len scalars, back to back from the aligned x, in one launch
+template <typename T> int ew_window_rows(T* x, size_t rows, size_t row_len, bool is_complex, int id, T alpha, bool unapply, hipStream_t s)
+{
+    if (rows == 0 || row_len == 0) return BDSP_OK;
+    size_t points = is_complex ? row_len / 2 : row_len;
+    return launch_map<T, OpWindow<T, true>>(x, rows * row_len, {id, alpha, points, (int)is_complex, (int)unapply, row_len}, s);
 }
 template <typename T> int ew_fill(T* x, size_t len, T value, hipStream_t s)
 { return launch_map<T, OpFill<T>>(x, len, {value}, s); }
 template <typename T> int ew_freq_response(T* x, size_t len, bool is_complex, int fid, T rolloff, T ratio, bool shifted, hipStream_t s)
 {
     size_t points = is_complex ? len / 2 : len;
-    return launch_map<T, OpFreqResp<T>>(x, len, {fid, rolloff, ratio, points, (int)is_complex, (int)shifted}, s);
+    return launch_map<T, OpFreqResp<T>>(x, len, {fid, rolloff, ratio, points, (int)is_complex, (int)shifted, len}, s);
+}
+template <typename T> int ew_freq_response_rows(T* x, size_t rows, size_t row_len, bool is_complex, int fid, T rolloff, T ratio, bool shifted, hipStream_t s)
+{
+    if (rows == 0 || row_len == 0) return BDSP_OK;
+    size_t points = is_complex ? row_len / 2 : row_len;
+    return launch_map<T, OpFreqResp<T, true>>(x, rows * row_len, {fid, rolloff, ratio, points, (int)is_complex, (int)shifted, row_len}, s);
 }
 template <typename T> int ew_linear_phase(T* x, size_t len, T delay, hipStream_t s)
 {
@@ -436,8 +460,10 @@ template <typename T> int ew_complex_to_real(const T* x, T* out, size_t len, int
     template int ew_mul_cexp<T>(T*, size_t, T, T, hipStream_t);                                    \
     template int ew_complex_to_real<T>(const T*, T*, size_t, int, hipStream_t);                    \
     template int ew_window<T>(T*, size_t, bool, int, T, bool, hipStream_t);                        \
+    template int ew_window_rows<T>(T*, size_t, size_t, bool, int, T, bool, hipStream_t);           \
     template int ew_fill<T>(T*, size_t, T, hipStream_t);                                            \
     template int ew_freq_response<T>(T*, size_t, bool, int, T, T, bool, hipStream_t);              \
+    template int ew_freq_response_rows<T>(T*, size_t, size_t, bool, int, T, T, bool, hipStream_t); \
     template int ew_linear_phase<T>(T*, size_t, T, hipStream_t);                                    \
     template int ew_spectrum_resample<T>(const T*, T*, size_t, size_t, int, int, T, T, double, hipStream_t);
 BDSP_INST(float)

@@ -259,7 +259,7 @@ void SFX(orc_swap_halves)(REAL *x, size_t len, int is_complex, int forward)
         /* cycle walk, mod.rs:181-189 */
         size_t step = forward ? n / 2 : n / 2 + 1;
         REAL temp[2] = { x[0], elem == 2 ? x[1] : (REAL)0 };
-        size_t pos = step;
+        size_t pos = step % n; /* (one point, backward: step == n) */
         for (size_t k = 0; k < n; ++k) {
             size_t pos_new = (pos + step) % n;
             for (size_t e = 0; e < elem; ++e) {

@@ -1,0 +1,624 @@
+"""The operations DspMat started with -- flat elementwise, complex -> real, index moves, windows,
+multiply_frequency_response, the six transforms, convolve_signal (shared filter and MIMO), interpolatef, get_row /
+set_row -- on rows that do NOT start on a 16-byte boundary: every row against the CPU oracle (numpy's FFT for the
+transforms) and, where the arithmetic is position-only, bit for bit against the vector path on that row; plus row
+isolation, result codes, poisoned and empty matrices.  Every tolerance is the one the vector test of the same
+operation in test_gpu_parity.py uses, named next to the assertion."""
+import numpy as np
+import pytest
+
+import oracle_lib as orc
+
+pytestmark = pytest.mark.gpu
+
+DTYPES = (np.float32, np.float64)
+TIME, FREQ = 0, 1
+PAD_END, PAD_SURROUND, PAD_CENTER = 0, 1, 2
+HAMMING = 1
+CONV_SINC, CONV_RAISED_COSINE = 0, 1
+EMPTY = ((5, 0), (0, 9))
+MANY_ROWS = (4097, 5)   # flat operations (one launch whatever the number of rows) only
+
+
+@pytest.fixture(scope="module")
+def bd():
+    import basic_dsp_amd as b
+    b.require_gpu()
+    return b
+
+
+def _offsets(rows, pts, dtype, cplx):
+    """bytes past a 16-byte boundary at which the rows start (the allocation itself is aligned)"""
+    return {r * pts * (2 if cplx else 1) * np.dtype(dtype).itemsize % 16 for r in range(rows)}
+
+
+def _shapes(dtype, cplx, many_rows=False):
+    """(rows, points per row).  Row lengths 1, 3, 5, 1001 (= 7 * 11 * 13: the general mixed-radix transform), 1009
+    (prime: Bluestein) and 4097, each with 1, 2 and 5 rows: five odd-length real f32 rows start 0, 4, 8, 12 and 0
+    bytes past a 16-byte boundary, complex f32 and real f64 rows 0 and 8 bytes; complex f64 rows are always aligned
+    and run as a control, like (3, 1000) and (2, 4096).  Rows stay few: several operations launch once per row."""
+    s = [(rows, pts) for pts in (1, 3, 5, 1001, 1009, 4097) for rows in (1, 2, 5)] + [(3, 1000), (2, 4096)]
+    want = {np.float32: {False: {0, 4, 8, 12}, True: {0, 8}}, np.float64: {False: {0, 8}, True: {0}}}[dtype][cplx]
+    for pts in (3, 5, 1001, 1009, 4097):
+        assert _offsets(5, pts, dtype, cplx) == want, (pts, dtype, cplx)
+    return s + ([MANY_ROWS] if many_rows else [])
+
+
+def _fill(rows, pts, seed, dtype, cplx, lo=-10, hi=10):
+    e = 2 if cplx else 1
+    return orc.fill_uniform(rows * pts * e, seed, lo, hi, dtype).reshape(rows, pts * e)
+
+
+def _mat(bd, x, cplx, **kw):
+    if x.size == 0:
+        return bd.DspMat(rows=x.shape[0], row_len=x.shape[1], is_complex=cplx, dtype=x.dtype, **kw)
+    return bd.DspMat(x, is_complex=cplx, **kw)
+
+
+def _per_row(fn, x):
+    """the oracle row by row; for the many-row shape, whose operations do not look at the position in a row, on the
+    flat data (the same arithmetic on the same elements, without 4097 calls)"""
+    if x.shape[0] > 300:
+        return fn(x.reshape(-1)).reshape(x.shape[0], -1)
+    return np.stack([fn(r) for r in x]) if x.shape[0] else x.copy()
+
+
+def _vector_path_rows(rows):
+    """rows whose result is compared bit for bit with the vector path: EVERY row, except for the many-row shape (one
+    DspVec per row would be 4097 of them), where it is the first 16, which start at every offset from a 16-byte
+    boundary, the last 16 and 16 spread in between; the oracle comparison covers all of its rows"""
+    if rows <= 300:
+        return list(range(rows))
+    return sorted(set(range(16)) | set(range(rows - 16, rows)) | set(np.linspace(0, rows - 1, 16).astype(int).tolist()))
+
+
+def _shape_ok(m, rows, row_len):
+    return m.rows() == rows and m.row_len() == (row_len if rows else 0) and m.data().shape == (rows, row_len if rows else 0)
+
+
+def _poisoned(m):
+    return m.row_len() == 0 and np.isnan(m.delta())
+
+
+def _as_real(a):
+    a = np.asarray(a)
+    if np.iscomplexobj(a):
+        return np.ascontiguousarray(a.astype(np.complex128)).view(np.float64)
+    return a.astype(np.float64)
+
+
+def rel_l2(got, ref):
+    got, ref = _as_real(got), _as_real(ref)
+    return np.linalg.norm(got - ref) / max(np.linalg.norm(ref), 1e-300)
+
+
+def tol_for(dtype):   # test_gpu_parity.py: rel-L2 of one f32 / f64 transform or convolution against the f64 oracle
+    return 1e-6 if dtype == np.float32 else 1e-12
+
+
+def _rows_close(got, ref, tol, what):
+    """rel_l2 < tol for EVERY row (one wrong row of five must fail, which a norm over the matrix would hide); where the
+    reference is NaN (the Hamming window of a single point is 0 / 0) the result must be NaN too"""
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    for r in range(ref.shape[0]):
+        g, f = _as_real(got[r]), _as_real(ref[r])
+        nan = np.isnan(f)
+        assert np.array_equal(np.isnan(g), nan), (what, r)
+        if not nan.all():
+            err = rel_l2(g[~nan], f[~nan])
+            assert err < tol, (what, r, err)
+
+
+# ---------------------------------------------------------------------------------------------- flat elementwise
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cplx", (False, True))
+def test_flat_elementwise_ops_equal_the_oracle_bit_for_bit(bd, dtype, cplx):
+    eps = np.finfo(dtype).eps
+    for k, (rows, pts) in enumerate(_shapes(dtype, cplx, many_rows=True)):
+        x = _fill(rows, pts, 1000 + k, dtype, cplx)
+        b = _fill(rows, pts, 2000 + k, dtype, cplx)
+        rl = x.shape[1]
+        m = _mat(bd, x, cplx)
+        assert m.scale(2.5) == 0 and m.offset(-1.25) == 0 and _shape_ok(m, rows, rl)
+        ref = _per_row(lambda r: orc.real_offset(orc.real_scale(r, 2.5), -1.25, cplx), x)
+        assert np.array_equal(m.data(), ref), ("scale, offset", rows, pts)
+        m = _mat(bd, x, cplx)
+        if cplx:
+            assert m.scale(complex(0.5, -1.5)) == 0
+            assert np.array_equal(m.data(), _per_row(lambda r: orc.complex_scale(r, 0.5, -1.5), x)), (rows, pts)
+            assert m.conj() == 0
+            assert np.array_equal(m.data(), _per_row(lambda r: orc.conj(orc.complex_scale(r, 0.5, -1.5)), x)), (rows, pts)
+        else:   # a complex factor / conj on a real matrix poison it
+            assert m.scale(complex(0.5, -1.5)) == -1 and _poisoned(m) and m.rows() == rows
+            m = _mat(bd, x, cplx)
+            assert m.conj() == -1 and _poisoned(m)
+        for op, name in enumerate(("add", "sub", "mul", "div")):
+            for other in ("matrix", "vector"):
+                m = _mat(bd, x, cplx)
+                if other == "matrix":
+                    assert getattr(m, name)(_mat(bd, b, cplx)) == 0
+                    if rows > 300:
+                        ref = orc.binary(x.reshape(-1), b.reshape(-1), cplx, op)[1].reshape(rows, rl)
+                    else:
+                        ref = np.stack([orc.binary(p, q, cplx, op)[1] for p, q in zip(x, b)])
+                else:
+                    assert getattr(m, name)(bd.DspVec(b[0], is_complex=cplx)) == 0
+                    if rows > 300:
+                        ref = orc.binary(x.reshape(-1), np.tile(b[0], rows), cplx, op)[1].reshape(rows, rl)
+                    else:
+                        ref = np.stack([orc.binary(p, b[0], cplx, op)[1] for p in x])
+                assert _shape_ok(m, rows, rl) and m.is_complex() == cplx
+                if name == "div" and cplx:   # test_complex_elementwise_bit_exact
+                    np.testing.assert_allclose(m.data(), ref, rtol=4 * eps, err_msg=str((other, rows, pts)))
+                else:
+                    assert np.array_equal(m.data(), ref), (name, other, rows, pts)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_complex_to_real_maps(bd, dtype):
+    eps = np.finfo(dtype).eps
+    for k, (rows, pts) in enumerate(_shapes(dtype, True, many_rows=True)):
+        x = _fill(rows, pts, 3000 + k, dtype, True)
+        for kind, name in enumerate(("magnitude", "magnitude_squared", "to_real", "to_imag", "phase")):
+            m = _mat(bd, x, True, domain=FREQ, delta=0.5)
+            assert getattr(m, name)() == 0
+            assert _shape_ok(m, rows, pts) and m.row_points() == pts and not m.is_complex()
+            assert m.domain() == FREQ and m.delta() == 0.5
+            ref = _per_row(lambda r: orc.complex_to_real(r, kind), x)
+            if kind in (1, 2, 3):
+                assert np.array_equal(m.data(), ref), (name, rows, pts)
+            else:   # test_complex_to_real_maps
+                np.testing.assert_allclose(m.data(), ref, rtol=4 * eps, atol=4 * eps, err_msg=str((name, rows, pts)))
+            real = _mat(bd, x, False)   # assert_complex! poisons
+            assert getattr(real, name)() == -1 and _poisoned(real) and real.rows() == rows
+
+
+# ---------------------------------------------------------------------------------------------- index moves
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cplx", (False, True))
+def test_swap_halves_shifts_and_zero_pad_bit_exact(bd, dtype, cplx):
+    for k, (rows, pts) in enumerate(_shapes(dtype, cplx)):
+        x = _fill(rows, pts, 4000 + k, dtype, cplx)
+        e = 2 if cplx else 1
+        for name, fwd in (("swap_halves", True), ("fft_shift", True), ("ifft_shift", False)):
+            m = _mat(bd, x, cplx)
+            assert getattr(m, name)() == 0 and _shape_ok(m, rows, pts * e)
+            assert np.array_equal(m.data(), np.stack([orc.swap_halves(r, cplx, fwd) for r in x])), (name, rows, pts)
+        m = _mat(bd, x, cplx)
+        assert m.fft_shift() == 0 and m.ifft_shift() == 0
+        assert np.array_equal(m.data(), x), (rows, pts)   # (odd and even lengths: the two shifts differ for odd ones)
+        for new_pts in (pts + 1, pts + 37, 2 * pts + 1):
+            for opt in (PAD_END, PAD_SURROUND, PAD_CENTER):
+                m = _mat(bd, x, cplx)
+                assert m.zero_pad(new_pts, opt) == 0
+                assert _shape_ok(m, rows, new_pts * e) and m.row_points() == new_pts and m.is_complex() == cplx
+                ref = np.stack([orc.zero_pad(r, cplx, new_pts, opt, buffered=(opt == PAD_SURROUND))[1] for r in x])
+                assert np.array_equal(m.data(), ref), (rows, pts, new_pts, opt)
+        m = _mat(bd, x, cplx)
+        for opt in (PAD_END, PAD_SURROUND, PAD_CENTER):
+            assert m.zero_pad(pts, opt) == 7 and m.zero_pad(pts - 1, opt) == 7   # InvalidArgumentLength
+        assert np.array_equal(m.data(), x)
+
+
+# ---------------------------------------------------------------------------------------------- windows
+def _ulp_of_10(dtype):
+    return float(np.spacing(np.asarray(10.0, dtype=dtype)))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cplx", (False, True))
+def test_windows_on_every_row(bd, dtype, cplx):
+    """apply_window / unapply_window are ONE launch over the flat allocation (the position in the row is the index
+    modulo row_len), so the many-row shape runs here too.  Tolerances: test_windows'."""
+    for k, (rows, pts) in enumerate(_shapes(dtype, cplx, many_rows=True)):
+        x = _fill(rows, pts, 5000 + k, dtype, cplx)
+        for wid in range(5):
+            ulps = 30 if wid == 2 else 4
+            oid, alpha = (1, 0.5) if wid == 4 else (wid, 0.54)
+            m = _mat(bd, x, cplx)
+            assert m.apply_window(wid) == 0 and _shape_ok(m, rows, x.shape[1]) and m.is_complex() == cplx
+            got = m.data()
+            ref = np.stack([orc.apply_window(r, cplx, oid, alpha) for r in x])
+            np.testing.assert_allclose(got, ref, rtol=0, atol=ulps * _ulp_of_10(dtype), err_msg=str((wid, rows, pts)))
+            assert m.unapply_window(wid) == 0
+            back = m.data()
+            with np.errstate(all="ignore"):
+                ref_back = np.stack([orc.apply_window(r, cplx, oid, alpha, unapply=True) for r in ref])
+                w = orc.apply_window(np.ones_like(x[0]), cplx, oid, alpha).astype(np.float64)
+            ok = np.abs(w) > 1e-2
+            np.testing.assert_allclose(back.astype(np.float64)[:, ok], ref_back.astype(np.float64)[:, ok], rtol=0,
+                                       atol=4 * ulps * _ulp_of_10(dtype) / 1e-2, err_msg=str((wid, rows, pts)))
+            # test_windows also demands that the mask keeps most of the row and that the row comes back; with 1, 3 and
+            # 5 points a window can be (almost) zero everywhere (Hann and Blackman-Harris end at 0, one point is 0 / 0),
+            # so both hold from 1000 points on and the short rows rest on the bit-identity with the vector path below
+            if pts >= 1000:
+                assert ok.sum() > 0.7 * ok.size, (wid, rows, pts)
+                for r in range(rows):
+                    assert rel_l2(back[r][ok], x[r][ok]) < (3e-6 if dtype == np.float32 else 1e-14), (wid, rows, pts, r)
+            # the window value depends on the position in the row alone: every row is the vector path's, bit for bit
+            # (all rows; the many-row shape is sampled, see _vector_path_rows)
+            for r in _vector_path_rows(rows):
+                v = bd.DspVec(x[r], is_complex=cplx)
+                assert v.apply_window(wid) == 0
+                assert np.array_equal(v.data(), got[r], equal_nan=True), (wid, rows, pts, r)
+                assert v.unapply_window(wid) == 0
+                assert np.array_equal(v.data(), back[r], equal_nan=True), (wid, rows, pts, r)
+
+
+# ---------------------------------------------------------------------------------------------- frequency response
+MFR_RATIO, MFR_ROLLOFF = 1.7, 0.35
+# f32: the project had no tolerance.  On exactly these inputs (_mfr_cases, all shapes, both functions, real and
+# complex) the DspVec path of the parent commit is at most MFR_F32_MEASURED_ULPS ulp of max |reference row| from the
+# oracle (measured on an MI355X); the bound is twice that and not less than 4 ulp.
+MFR_F32_MEASURED_ULPS = 1.0
+MFR_F32_BOUND_ULPS = max(2 * MFR_F32_MEASURED_ULPS, 4.0)
+
+
+def _mfr_cases(dtype, cplx):
+    """(rows, pts, fid, input in [-1, 1), oracle result): shared by the test and by the measurement of the f32 bound"""
+    for k, (rows, pts) in enumerate(_shapes(dtype, cplx, many_rows=True)):
+        x = _fill(rows, pts, 6000 + k, dtype, cplx, -1, 1)
+        for fid in (CONV_SINC, CONV_RAISED_COSINE):
+            ref = np.stack([orc.multiply_frequency_response(r, cplx, fid, MFR_ROLLOFF, MFR_RATIO, False) for r in x])
+            yield rows, pts, fid, x, ref
+
+
+def _ulps_of_max(got, ref):
+    """largest |got - ref| of a row in ulps of that row's max |ref| (of 1 if the row is all zero)"""
+    top = np.max(np.abs(ref.astype(np.float64)))
+    ulp = float(np.spacing(np.asarray(top if top > 0 else 1.0, dtype=ref.dtype)))
+    return float(np.max(np.abs(got.astype(np.float64) - ref.astype(np.float64)))) / ulp
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cplx", (False, True))
+def test_multiply_frequency_response_on_every_row(bd, dtype, cplx):
+    worst = 0.0
+    for rows, pts, fid, x, ref in _mfr_cases(dtype, cplx):
+        m = _mat(bd, x, cplx, domain=FREQ, delta=0.25)
+        assert m.multiply_frequency_response(fid, MFR_RATIO, MFR_ROLLOFF) == 0
+        assert _shape_ok(m, rows, x.shape[1]) and m.is_complex() == cplx and m.domain() == FREQ and m.delta() == 0.25
+        got = m.data()
+        if dtype == np.float64:   # test_multiply_frequency_response_gpu
+            np.testing.assert_allclose(got, ref, rtol=0, atol=1e-12, err_msg=str((rows, pts, fid)))
+        else:
+            for r in range(rows):
+                u = _ulps_of_max(got[r], ref[r])
+                worst = max(worst, u)
+                assert u <= MFR_F32_BOUND_ULPS, (rows, pts, fid, r, u)   # measured 1.0 ulp, bound max(2 x 1.0, 4) = 4 ulp
+        # the response depends on the position in the row alone: every row is the vector path's, bit for bit (all rows;
+        # the many-row shape is sampled, see _vector_path_rows)
+        for r in _vector_path_rows(rows):
+            v = bd.DspVec(x[r], is_complex=cplx, domain=FREQ)
+            assert v.multiply_frequency_response(fid, MFR_RATIO, MFR_ROLLOFF) == 0
+            assert np.array_equal(v.data(), got[r]), (rows, pts, fid, r)
+    if dtype == np.float32:
+        print("multiply_frequency_response f32 cplx=%d: at most %.3f ulp of max |ref| from the oracle" % (cplx, worst))
+
+
+def test_multiply_frequency_response_known_answers_on_every_row(bd):
+    m = bd.DspMat(np.ones((3, 10), np.float32), is_complex=True, domain=FREQ)
+    assert m.multiply_frequency_response(CONV_RAISED_COSINE, 2.0, 1.0) == 0
+    for row in m.data():   # convolution.rs:633-639, as test_multiply_frequency_response_gpu
+        np.testing.assert_allclose(row, [0, 0, 1, 1, 2, 2, 1, 1, 0, 0], atol=1e-4)
+
+
+# ---------------------------------------------------------------------------------------------- transforms
+def _to_complex(x, cplx):
+    """rows as float64 interleaved complex (a real row is zero-interleaved first, time_to_freq.rs:147-150)"""
+    xd = x.astype(np.float64)
+    if cplx:
+        return xd
+    out = np.zeros((x.shape[0], 2 * x.shape[1]))
+    out[:, 0::2] = xd
+    return out
+
+
+def _np_fft(row, inverse=False):
+    """unnormalised DFT of an interleaved float64 row (numpy stands in for the oracle:
+    test_fft_matches_oracle_restatement_small)"""
+    z = np.ascontiguousarray(row).view(np.complex128)
+    return np.ascontiguousarray(np.fft.ifft(z) * z.size if inverse else np.fft.fft(z)).view(np.float64)
+
+
+def _forward_ref(row, name):
+    if name == "plain_fft":
+        return _np_fft(row)
+    if name == "windowed_fft":
+        with np.errstate(all="ignore"):
+            row = orc.apply_window(row, True, 1, 0.54)
+    return orc.swap_halves(_np_fft(row), True, True)
+
+
+def _inverse_ref(row, name):
+    """plain_ifft is unnormalised; ifft = scale(1 / n) -> ifft_shift -> plain_ifft (freq_to_time.rs:160-168); the
+    windowed one divides by the window afterwards"""
+    if name == "plain_ifft":
+        return _np_fft(row, True)
+    n = row.size // 2
+    out = _np_fft(orc.swap_halves(row, True, False), True) / n
+    if name == "windowed_ifft":
+        with np.errstate(all="ignore"):
+            out = orc.apply_window(out, True, 1, 0.54, unapply=True)
+    return out
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cplx", (False, True))
+def test_transforms_of_every_row(bd, dtype, cplx):
+    """The forward transforms on real and complex rows, then the matching inverse on the result (a round trip), and the
+    inverses on their own on real and complex frequency-domain rows (a real spectrum is zero-interleaved to complex
+    first, freq_to_time.rs:149-152, fused with the input shift and the 1 / n scale).  delta() == n * delta exactly, in
+    the matrix's number format: 0.25 * n is exact, 0.25 * 4097 * 4097 needs 25 bits and rounds in float32."""
+    tol = tol_for(dtype)
+    pairs = (("plain_fft", "plain_ifft", ()), ("fft", "ifft", ()), ("windowed_fft", "windowed_ifft", (HAMMING,)))
+    for k, (rows, pts) in enumerate(_shapes(dtype, cplx)):
+        x = _fill(rows, pts, 7000 + k, dtype, cplx)
+        xc = _to_complex(x, cplx)
+        delta1 = dtype(pts) * dtype(0.25)
+        delta2 = dtype(pts) * delta1
+        assert float(delta1) == 0.25 * pts
+        for fwd, inv, args in pairs:
+            m = _mat(bd, x, cplx, delta=0.25)
+            assert getattr(m, fwd)(*args) == 0
+            assert m.is_complex() and m.domain() == FREQ and m.delta() == float(delta1)
+            assert m.rows() == rows and m.row_points() == pts and m.row_len() == 2 * pts
+            ref = np.stack([_forward_ref(r, fwd) for r in xc])
+            _rows_close(m.data(), ref, tol, (fwd, rows, pts))
+            assert getattr(m, inv)(*args) == 0
+            assert m.is_complex() and m.domain() == TIME and m.delta() == float(delta2)
+            assert m.rows() == rows and m.row_points() == pts
+            back = m.data().astype(np.float64) / (pts if fwd == "plain_fft" else 1)
+            expect = xc.copy()
+            if fwd == "windowed_fft" and pts == 1:
+                expect[:] = np.nan   # the Hamming window of one point is 0 / 0
+            _rows_close(back, expect, 2 * tol, (fwd + " -> " + inv, rows, pts))
+        for _, inv, args in pairs:
+            m = _mat(bd, x, cplx, domain=FREQ, delta=0.25)
+            assert getattr(m, inv)(*args) == 0
+            assert m.is_complex() and m.domain() == TIME and m.delta() == float(delta1)
+            assert m.rows() == rows and m.row_points() == pts and m.row_len() == 2 * pts
+            with np.errstate(all="ignore"):
+                ref = np.stack([_inverse_ref(r, inv) for r in xc])
+            _rows_close(m.data(), ref, tol, (inv, rows, pts))
+
+
+# ---------------------------------------------------------------------------------------------- convolution
+CONV_SHAPES = ((5, 4097, 33), (3, 9001, 1024), (5, 1001, 3), (2, 7001, 3100), (5, 101, 17))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cplx", (False, True))
+def test_convolve_signal_with_a_shared_filter(bd, dtype, cplx):
+    """Block kernel with few and many taps, rows of fewer points than one 4096-point block, the long-filter path (3100
+    taps); real rows travel two blocks to a complex transform.  Filters scaled by 1 / taps, tolerance and reference as
+    test_convolve_signal_complex_vs_direct_oracle."""
+    e = 2 if cplx else 1
+    for k, (rows, pts, taps) in enumerate(CONV_SHAPES):
+        x = _fill(rows, pts, 8000 + k, dtype, cplx)
+        h = orc.fill_uniform(taps * e, 8100 + k, -1, 1, dtype) / dtype(taps)
+        m = _mat(bd, x, cplx)
+        assert m.convolve_signal(bd.DspVec(h, is_complex=cplx)) == 0
+        assert _shape_ok(m, rows, pts * e) and m.is_complex() == cplx and m.domain() == TIME
+        ref = np.stack([orc.convolve_direct(r.astype(np.float64), h.astype(np.float64), cplx) for r in x])
+        _rows_close(m.data(), ref, tol_for(dtype), (rows, pts, taps))
+    x = _fill(5, 101, 1, dtype, cplx)
+    m = _mat(bd, x, cplx)
+    assert m.convolve_signal(bd.DspVec(np.ones(102 * e, dtype), is_complex=cplx)) == 7   # filter longer than a row
+    assert m.convolve_signal(bd.DspVec(np.ones(6, dtype), is_complex=not cplx)) == 2       # number spaces differ
+    assert np.array_equal(m.data(), x)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("rows,pts,taps,cplx", ((3, 1001, 17, False), (2, 4097, 33, True)))
+def test_convolve_signal_mimo(bd, dtype, rows, pts, taps, cplx):
+    """out[n] = sum_r row[r] (*) h[n][r]: one launch per (n, r) on row pointers that are not 16-byte aligned, and a
+    vectorised sum into an unaligned output row.  Reference and tolerance as test_matrix_convolve_signal_mimo_kats."""
+    e = 2 if cplx else 1
+    x = _fill(rows, pts, 9000, dtype, cplx)
+    hs = [[orc.fill_uniform(taps * e, 9100 + 10 * n + r, -1, 1, dtype) / dtype(taps) for r in range(rows)] for n in range(rows)]
+    m = _mat(bd, x, cplx)
+    assert m.convolve_signal([[bd.DspVec(h, is_complex=cplx) for h in row] for row in hs]) == 0
+    assert _shape_ok(m, rows, pts * e) and m.is_complex() == cplx
+    ref = np.stack([sum(orc.convolve_direct(x[r].astype(np.float64), hs[n][r].astype(np.float64), cplx) for r in range(rows))
+                    for n in range(rows)])
+    _rows_close(m.data(), ref, tol_for(dtype), (rows, pts, taps))
+
+
+# ---------------------------------------------------------------------------------------------- interpolatef
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cplx", (False, True))
+def test_interpolatef_of_every_row(bd, dtype, cplx):
+    """Input AND output rows off the 16-byte grid.  Integer factor: reference and tolerance of
+    test_matrix_batched_ops_equal_per_row_vector_ops (the float64 oracle, 2e-6 / 1e-12); fractional factor: those of
+    test_interpolatef_fractional_factor_packed_kernel (the oracle in T with exact weights, 2e-6 / 1e-12)."""
+    tol = 2e-6 if dtype == np.float32 else 1e-12
+    for k, (rows, pts) in enumerate(((5, 1001), (5, 333), (2, 1001))):
+        x = _fill(rows, pts, 10000 + k, dtype, cplx)
+        for fid, rolloff, factor, conv_len in ((CONV_SINC, 0.0, 2.0, 8), (CONV_RAISED_COSINE, 0.35, 1.5, 10)):
+            m = _mat(bd, x, cplx, delta=1.0)
+            assert m.interpolatef(fid, factor, 0.0, conv_len, rolloff) == 0
+            new_len = orc.interpolatef_new_len(x.shape[1], dtype(factor), dtype)
+            assert new_len % 2 == 0 and _shape_ok(m, rows, new_len) and m.is_complex() == cplx and m.delta() == 1.0
+            if factor == 2.0:
+                ref = np.stack([orc.interpolatef(r.astype(np.float64), cplx, fid, rolloff, factor, 0.0, conv_len)[0] for r in x])
+            else:
+                with orc.exact_weights():
+                    ref = np.stack([orc.interpolatef(r, cplx, fid, rolloff, dtype(factor), 0.0, conv_len)[0] for r in x])
+            _rows_close(m.data(), ref, tol, (rows, pts, fid, factor))
+
+
+# ---------------------------------------------------------------------------------------------- rows in and out
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cplx", (False, True))
+def test_get_row_and_set_row(bd, dtype, cplx):
+    rows, pts = 5, 1001
+    x = _fill(rows, pts, 11000, dtype, cplx)
+    y = _fill(rows, pts, 11001, dtype, cplx)
+    m = _mat(bd, x, cplx, domain=FREQ, delta=0.5)
+    for r in range(rows):
+        v = m.get_row(r)
+        assert np.array_equal(v.data(), x[r]), r
+        assert v.is_complex() == cplx and v.domain() == FREQ and v.delta() == 0.5 and v.points() == pts
+    with pytest.raises(IndexError):
+        m.get_row(rows)
+    expect = x.copy()
+    for r in (3, 0, 4, 1, 2):
+        assert m.set_row(r, bd.DspVec(y[r], is_complex=cplx)) == 0
+        expect[r] = y[r]
+        assert m.data().tobytes() == expect.tobytes(), r   # row r and no other byte
+    assert m.set_row(0, bd.DspVec(y[0][:-2], is_complex=cplx)) == 7
+    assert m.set_row(rows, bd.DspVec(y[0], is_complex=cplx)) == 7
+    assert m.data().tobytes() == expect.tobytes() and _shape_ok(m, rows, x.shape[1])
+
+
+# ---------------------------------------------------------------------------------------------- row isolation
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cplx", (False, True))
+def test_rows_are_isolated(bd, dtype, cplx):
+    """One row of the input replaced (other values, an inf and a NaN among them): every other row of the output is
+    bit-identical to the first run.  test_gpu_mat_scan.py::test_rows_are_isolated is the model."""
+    e = 2 if cplx else 1
+    h33 = bd.DspVec(orc.fill_uniform(33 * e, 5, -1, 1, dtype) / dtype(33), is_complex=cplx)
+    h1024 = bd.DspVec(orc.fill_uniform(1024 * e, 6, -1, 1, dtype) / dtype(1024), is_complex=cplx)
+    ops = [("apply_window", TIME, lambda m: m.apply_window(2)), ("unapply_window", TIME, lambda m: m.unapply_window(1)),
+           ("multiply_frequency_response", FREQ, lambda m: m.multiply_frequency_response(CONV_RAISED_COSINE, MFR_RATIO, MFR_ROLLOFF)),
+           ("plain_fft", TIME, lambda m: m.plain_fft()), ("fft", TIME, lambda m: m.fft()),
+           ("windowed_fft", TIME, lambda m: m.windowed_fft(HAMMING)), ("windowed_ifft", FREQ, lambda m: m.windowed_ifft(HAMMING)),
+           ("plain_ifft", FREQ, lambda m: m.plain_ifft()), ("ifft", FREQ, lambda m: m.ifft()),
+           ("convolve_signal 33", TIME, lambda m: m.convolve_signal(h33)),
+           ("convolve_signal 1024", TIME, lambda m: m.convolve_signal(h1024))]
+    for rows, pts in ((5, 1001), (5, 1009), (5, 4097), (2, 4096)):
+        x = _fill(rows, pts, 12000 + pts, dtype, cplx)
+        r0 = rows // 2
+        bad = x.copy()
+        bad[r0] = _fill(1, pts, 12001 + pts, dtype, cplx, -1e3, 1e3)[0]
+        bad[r0, 0], bad[r0, pts // 2], bad[r0, -1] = np.inf, np.nan, 1e30
+        others = np.arange(rows) != r0
+        for name, domain, op in ops:
+            if name.endswith("1024") and pts < 1024:
+                continue   # (a filter may not be longer than the rows)
+            res = []
+            for data in (x, bad):
+                m = _mat(bd, data, cplx, domain=domain)
+                assert op(m) == 0, name
+                res.append(m.data())
+            assert res[0][others].tobytes() == res[1][others].tobytes(), (name, rows, pts)
+            assert res[0][r0].tobytes() != res[1][r0].tobytes(), (name, rows, pts)
+
+
+# ---------------------------------------------------------------------------------------------- codes and state
+def _every_call(bd, m, dtype, cplx):
+    """(name, call) for every operation of this file on matrix m, with operands of m's CURRENT shape where an operand
+    of another size would be an argument error (which comes before the poison check, as in the reference's facade)"""
+    rows, rl = m.rows(), m.row_len()
+    zm = lambda: bd.DspMat(rows=rows, row_len=rl, is_complex=cplx, dtype=dtype, domain=m.domain())
+    zv = lambda n=rl: bd.DspVec(np.zeros(n, dtype), is_complex=cplx, domain=m.domain())
+    calls = [("scale", lambda: m.scale(2.0)), ("offset", lambda: m.offset(1.0))]
+    if cplx:
+        calls += [("complex scale", lambda: m.scale(complex(1.0, 2.0))), ("conj", lambda: m.conj())]
+    for name in ("add", "sub", "mul", "div"):
+        calls += [(name, lambda name=name: getattr(m, name)(zm())), (name + " vector", lambda name=name: getattr(m, name)(zv()))]
+    calls += [(n, getattr(m, n)) for n in ("swap_halves", "fft_shift", "ifft_shift")]
+    calls += [("apply_window %d" % w, lambda w=w: m.apply_window(w)) for w in range(5)]
+    calls += [("unapply_window %d" % w, lambda w=w: m.unapply_window(w)) for w in range(5)]
+    calls += [("interpolatef", lambda: m.interpolatef(CONV_SINC, 2.0, 0.0, 8)),
+              ("interpolatef rc", lambda: m.interpolatef(CONV_RAISED_COSINE, 1.5, 0.0, 10, 0.35)),
+              ("set_row", lambda: m.set_row(0, zv()))]
+    return calls
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_codes(bd, dtype):
+    x = _fill(5, 1001, 13000, dtype, False)
+    m = _mat(bd, x, False)
+    assert m.add(_mat(bd, x[:4], False)) == 7 and m.mul(_mat(bd, x[:4], False)) == 7        # row counts differ
+    assert m.add(_mat(bd, x[:, :-1], False)) == 1                                           # same rows, other length
+    assert m.add(bd.DspVec(x[0][:-1])) == 1 and m.div(bd.DspVec(np.ones(1002, dtype))) == 1
+    for other in (dict(delta=2.0), dict(domain=FREQ)):                                      # meta data must agree
+        assert m.add(bd.DspMat(x, **other)) == 2 and m.sub(bd.DspVec(x[0], **other)) == 2
+    assert m.add(bd.DspMat(x[:, :-1], is_complex=True)) == 1 and m.add(bd.DspVec(x[0][:-1], is_complex=True)) == 1
+    assert np.array_equal(m.data(), x)                                                      # nothing was touched
+    assert m.mul(bd.DspMat(x, delta=1.05)) == 0                                             # a delta ratio within 0.9 .. 1.1 agrees
+    # the transforms' type state: forward needs the time domain, inverse the frequency domain
+    for name, domain in (("plain_fft", FREQ), ("fft", FREQ), ("windowed_fft", FREQ), ("plain_ifft", TIME), ("ifft", TIME), ("windowed_ifft", TIME)):
+        m = _mat(bd, x, False, domain=domain)
+        args = (HAMMING,) if "windowed" in name else ()
+        assert getattr(m, name)(*args) == -1 and _poisoned(m) and m.rows() == 5
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cplx", (False, True))
+def test_a_poisoned_matrix_reports_minus_one_from_every_call(bd, dtype, cplx):
+    e = 2 if cplx else 1
+    x = _fill(5, 1001, 14000, dtype, cplx)
+
+    def poisoned():
+        m = _mat(bd, x, cplx)
+        assert m.multiply_frequency_response(CONV_SINC, 0.5) == -1 and _poisoned(m) and m.rows() == 5   # time domain
+        return m
+
+    m = poisoned()
+    for name, call in _every_call(bd, m, dtype, cplx):
+        assert call() == -1, name
+        assert _poisoned(m) and m.rows() == 5 and m.is_complex() == cplx, name
+    assert m.multiply_frequency_response(CONV_SINC, 0.5) == -1
+    for opt in (PAD_END, PAD_SURROUND, PAD_CENTER):
+        assert m.zero_pad(8, opt) == -1 and _poisoned(m), opt   # (does not revive the matrix with rows of zeros)
+        assert m.zero_pad(0, opt) == 7 and _poisoned(m), opt    # an argument error comes first
+    assert m.convolve_signal(bd.DspVec(np.zeros(0, dtype), is_complex=cplx)) == -1
+    assert m.convolve_signal(bd.DspVec(np.ones(3 * e, dtype), is_complex=cplx)) == 7         # an argument error comes first
+    assert m.convolve_signal([[bd.DspVec(np.ones(3 * e, dtype), is_complex=cplx) for _ in range(5)] for _ in range(5)]) == -1
+    assert m.data().shape == (5, 0) and m.get_row(4).is_erroneous()
+    for name in ("magnitude", "magnitude_squared", "to_real", "to_imag", "phase"):
+        m = poisoned()
+        assert getattr(m, name)() == -1 and _poisoned(m) and not (cplx and m.is_complex()), name
+    for name in ("plain_fft", "fft", "windowed_fft", "plain_ifft", "ifft", "windowed_ifft"):
+        m = poisoned()
+        args = (HAMMING,) if "windowed" in name else ()
+        assert getattr(m, name)(*args) == -1 and _poisoned(m) and m.is_complex() and m.rows() == 5, name
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cplx", (False, True))
+@pytest.mark.parametrize("rows,pts", EMPTY)
+def test_empty_shapes_through_every_operation(bd, dtype, cplx, rows, pts):
+    """No rows, or rows without points (built with DspMat(rows=, row_len=, dtype=)): 0 or the documented code, rows()
+    and row_len() stay consistent, data() has the right shape.  A matrix without rows reports rows of length 0.  (A
+    transform of a matrix without rows used to divide by zero on the host.)"""
+    e = 2 if cplx else 1
+    new = lambda **kw: bd.DspMat(rows=rows, row_len=pts * e, is_complex=cplx, dtype=dtype, **kw)
+    m = new()
+    assert _shape_ok(m, rows, 0) and m.row_points() == 0 and not _poisoned(m)
+    for name, call in _every_call(bd, m, dtype, cplx):
+        assert call() == (7 if name == "set_row" and rows == 0 else 0), name
+        assert _shape_ok(m, rows, 0) and m.is_complex() == cplx and not _poisoned(m) and m.delta() == 1.0, name
+    if rows:
+        assert m.get_row(rows - 1).data().size == 0
+    with pytest.raises(IndexError):
+        m.get_row(rows)
+    for opt in (PAD_END, PAD_SURROUND, PAD_CENTER):
+        m = new()
+        assert m.zero_pad(0, opt) == 7
+        assert m.zero_pad(3, opt) == 0 and _shape_ok(m, rows, 3 * e) and m.row_points() == (3 if rows else 0)
+        assert not m.data().any()
+    m = new()
+    assert m.convolve_signal(bd.DspVec(np.zeros(0, dtype), is_complex=cplx)) == 0
+    assert m.convolve_signal(bd.DspVec(np.ones(3 * e, dtype), is_complex=cplx)) == 7         # filter longer than the rows
+    mimo = [[bd.DspVec(np.ones(3 * e, dtype), is_complex=cplx) for _ in range(rows)] for _ in range(rows)]
+    assert m.convolve_signal(mimo) == (0 if rows else 7)                                     # rows x rows responses, rows > 0
+    assert _shape_ok(m, rows, 0)
+    m = new(domain=FREQ)
+    for fid in (CONV_SINC, CONV_RAISED_COSINE):
+        assert m.multiply_frequency_response(fid, MFR_RATIO, MFR_ROLLOFF) == 0 and _shape_ok(m, rows, 0) and m.domain() == FREQ
+    for name in ("magnitude", "magnitude_squared", "to_real", "to_imag", "phase"):
+        m = new()
+        assert getattr(m, name)() == (0 if cplx else -1) and _shape_ok(m, rows, 0) and not m.is_complex(), name
+    for fwd, inv in (("plain_fft", "plain_ifft"), ("fft", "ifft"), ("windowed_fft", "windowed_ifft")):
+        args = (HAMMING,) if "windowed" in fwd else ()
+        m = new(delta=0.25)
+        assert getattr(m, fwd)(*args) == 0, fwd
+        assert _shape_ok(m, rows, 0) and m.is_complex() and m.domain() == FREQ and m.delta() == 0.25 and m.row_points() == 0, fwd
+        assert getattr(m, inv)(*args) == 0, inv
+        assert _shape_ok(m, rows, 0) and m.is_complex() and m.domain() == TIME and m.delta() == 0.25, inv
+        assert getattr(m, inv)(*args) == -1 and _poisoned(m) and m.rows() == rows, inv      # the time domain again

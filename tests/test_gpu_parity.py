@@ -1069,7 +1069,9 @@ def _mat_rows(rows, n, seed, dtype, cplx):
 def test_matrix_batched_ops_equal_per_row_vector_ops(dtype):
     from basic_dsp_amd import DspMat
     tol = 2e-6 if dtype == np.float32 else 1e-12
-    for cplx, rows, n in ((True, 3, 4096), (True, 5, 1000), (False, 4, 2048), (True, 2, 1 << 14)):
+    # (5 rows of 1001 points: rows that do not start on a 16-byte boundary, tests/test_gpu_mat_basic.py)
+    for cplx, rows, n in ((True, 3, 4096), (True, 5, 1000), (False, 4, 2048), (True, 2, 1 << 14), (False, 5, 1001),
+                          (True, 5, 1001)):
         a = _mat_rows(rows, n, 100 + n, dtype, cplx)
         # elementwise + complex->real: bit-exact against the oracle applied row by row
         m = DspMat(a, is_complex=cplx)
