@@ -307,6 +307,11 @@ for _s, _t, _R in (("32", _F, VectorInteropResult32), ("64", _D, VectorInteropRe
     _proto(_m + "interpolate" + _s, C.c_int32, _P, C.c_int32, _t, _SZ, _t)
     _proto(_m + "interpft" + _s, C.c_int32, _P, _SZ)
     _proto(_m + "decimatei" + _s, C.c_int32, _P, C.c_uint32, C.c_uint32)
+    # symmetric real-signal transforms of the rows, mirror, to_complex
+    for _n in ("plain_sfft", "sfft", "plain_sifft", "sifft", "mirror", "to_complex"):
+        _proto(_m + _n + _s, C.c_int32, _P)
+    for _n in ("windowed_sfft", "windowed_sifft"):
+        _proto(_m + _n + _s, C.c_int32, _P, C.c_int32)
 
 WINDOW_FN32 = C.CFUNCTYPE(_F, _P, _SZ, _SZ)
 WINDOW_FN64 = C.CFUNCTYPE(_D, _P, _SZ, _SZ)

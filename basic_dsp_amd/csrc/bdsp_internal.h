@@ -294,6 +294,15 @@ template <typename T>
 int rs_fused(const T* in, T* out, size_t rows, size_t points, size_t new_points, bool is_real, int mode, int fid,
              T rolloff, T ratio, double phase_inc, hipStream_t s);
 
+// mat_sym.hip -- the index moves of the symmetric real-signal transforms of a matrix; one launch each, whatever `rows`
+// rows of 2p - 1 complex bins -> rows of their first p bins, dense, out of place
+template <typename T> int sy_crop_rows(const T* in, T* out, size_t rows, size_t p, hipStream_t s);
+// rows of p complex bins -> rows of 2p - 1: h(j) = (scaled ? scale : 1) * in[(j + rot) mod p], out[g] = g < p ? h(g) :
+// conj(h(2p - 1 - g)), out of place; rot < p.  flag (device, zeroed by the caller; may be null): set to 1 if h(0) of any
+// row fails sy_first_bin_fails (mat_sym_core.h)
+template <typename T>
+int sy_mirror_rows(const T* in, T* out, size_t rows, size_t p, size_t rot, bool scaled, T scale, unsigned* flag, hipStream_t s);
+
 // bluestein.hip
 template <typename T> int bs_chirp(T* c, size_t n, bool inverse, hipStream_t s);
 template <typename T> int bs_kernel(const T* c, T* b, size_t n, size_t m, hipStream_t s);

@@ -2174,6 +2174,87 @@ int mat_decimatei(DevMat<T>* m, unsigned factor, unsigned delay)
     return BDSP_OK;
 }
 
+// Symmetric real-signal transforms of the rows (matrix/src/time_freq.rs:83-107, 144-168, 173-177 forward the traits row
+// by row): every row behaves as op_sfft / op_sifft / op_mirror would on it.  Forward: the batched real-input transform,
+// then one crop of every row to its first p = N/2 + 1 bins.  Inverse: one launch that scales, rotates, tests the first
+// bin of every row and mirrors to 2p - 1 bins, one 4-byte read-back (the call's only synchronisation), the batched
+// inverse transform with real output.  The launch counts do not depend on the row count; both buffers are reserved for
+// the larger shape, rows x (2p - 1) complex points, before the first launch.
+template <typename T>
+int mat_sfft(DevMat<T>* m, bool shift, int window)
+{
+    DevVec<T>* v = &m->v;
+    if (v->freq || v->complex_) { v->poison(); v->complex_ = true; v->freq = true; return BDSP_ERR_MUST_BE_TIME; }
+    const size_t rows = m->rows, n = m->row_len();
+    if (rows == 0) { v->valid_len = 0; v->complex_ = true; v->freq = true; return BDSP_OK; }
+    if (n % 2 == 0) { v->poison(); v->complex_ = true; v->freq = true; return BDSP_ERR_ODD_LENGTH; }
+    const size_t p = n / 2 + 1;
+    BDSP_TRY(v->reserve(rows * 2 * n));
+    BDSP_TRY(op_fft<T>(v, false, shift, window, rows)); // window, shift and delta <- n * delta as for complex rows
+    // unmirror! (time_to_freq.rs:178-186): the first p bins of every row; of the shifted forms that is the negative
+    // half plus DC, as op_sfft keeps it
+    BDSP_TRY(sy_crop_rows<T>(v->data, v->buf, rows, p, lib_stream()));
+    v->trade();
+    v->valid_len = rows * 2 * p;
+    return BDSP_OK;
+}
+
+template <typename T>
+int mat_sifft(DevMat<T>* m, bool shift, int window)
+{
+    DevVec<T>* v = &m->v;
+    if (!v->freq || !v->complex_) { v->poison(); v->complex_ = true; v->freq = true; return BDSP_ERR_MUST_BE_FREQ; }
+    const size_t rows = m->rows, p = m->row_points();
+    if (rows == 0 || p == 0) { v->valid_len = 0; v->complex_ = false; v->freq = false; return BDSP_OK; } // op_sifft on an empty vector
+    const size_t n = 2 * p - 1;
+    hipStream_t s = lib_stream();
+    BDSP_TRY(v->reserve(rows * 2 * n));
+    WsBlock flag;
+    BDSP_TRY(flag.alloc(sizeof(unsigned), s));
+    BDSP_HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(unsigned), s));
+    // sifft: scale(1/p) and ifft_shift of the HALF spectrum come first (freq_to_time.rs:226-236), so the symmetry
+    // test sees the first bin of the shifted half spectrum, as in op_sifft
+    BDSP_TRY(sy_mirror_rows<T>(v->data, v->buf, rows, p, shift ? p / 2 : 0, shift, shift ? (T)1 / (T)p : (T)1,
+                               flag.as<unsigned>(), s));
+    unsigned failed = 0;
+    BDSP_HIP_TRY(hipMemcpyAsync(&failed, flag.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    BDSP_HIP_TRY(hipStreamSynchronize(s));
+    if (failed) { v->poison(); v->complex_ = true; v->freq = true; return BDSP_ERR_CONJ_SYMMETRIC; }
+    v->trade();
+    v->valid_len = rows * 2 * n;
+    bool in_b = false;
+    BDSP_TRY(fft_two_buffers<T>(v->data, v->buf, n, rows, true, FFT_OUT_REAL, (T)1, -1, (T)0, &in_b, s));
+    if (in_b) v->trade();
+    v->valid_len = rows * n;
+    v->complex_ = false;
+    v->freq = false;
+    v->delta = (T)n * v->delta; // as op_fft
+    if (shift && window >= 0) {
+        // a separate launch: FFT_WINDOW_OUT_DIV is not combined with FFT_OUT_REAL on every transform path
+        int wid;
+        T alpha;
+        map_window<T>(window, &wid, &alpha);
+        BDSP_TRY(ew_window_rows<T>(v->data, rows, n, false, wid, alpha, true, s));
+    }
+    return BDSP_OK;
+}
+
+template <typename T>
+int mat_mirror(DevMat<T>* m)
+{
+    DevVec<T>* v = &m->v;
+    if (!v->freq && !v->complex_) { v->poison(); return BDSP_OK; } // freq.rs:56-59
+    const size_t rows = m->rows, rl = m->row_len(), p = rl / 2;
+    if (rl % 2 != 0) return BDSP_ERR_ARG_LENGTH; // real rows that hold no whole bins
+    if (rows == 0 || p == 0) return BDSP_OK;
+    const size_t n = 2 * p - 1;
+    BDSP_TRY(v->reserve(rows * 2 * n));
+    BDSP_TRY(sy_mirror_rows<T>(v->data, v->buf, rows, p, 0, false, (T)1, nullptr, lib_stream()));
+    v->trade();
+    v->valid_len = rows * 2 * n;
+    return BDSP_OK;
+}
+
 } // namespace
 
 // ==============================================================================================
@@ -2822,6 +2903,21 @@ BDSP_MAT_SCAN(64, double, MatBuf64)
 BDSP_MAT_RESAMPLE(32, float, MatBuf32)
 BDSP_MAT_RESAMPLE(64, double, MatBuf64)
 #undef BDSP_MAT_RESAMPLE
+
+// symmetric real-signal transforms of the rows, mirror, to_complex (mat_sfft / mat_sifft / mat_mirror above)
+#define BDSP_MAT_SYM(SFX, T, MB)                                                                            \
+    int32_t bdsp_hip_mat_plain_sfft##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_sfft<T>(a, false, -1)); } \
+    int32_t bdsp_hip_mat_sfft##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_sfft<T>(a, true, -1)); } \
+    int32_t bdsp_hip_mat_windowed_sfft##SFX(MB* m, int32_t window) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_sfft<T>(a, true, window < 0 ? 3 : window)); } \
+    int32_t bdsp_hip_mat_plain_sifft##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_sifft<T>(a, false, -1)); } \
+    int32_t bdsp_hip_mat_sifft##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_sifft<T>(a, true, -1)); } \
+    int32_t bdsp_hip_mat_windowed_sifft##SFX(MB* m, int32_t window) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_sifft<T>(a, true, window < 0 ? 3 : window)); } \
+    int32_t bdsp_hip_mat_mirror##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_mirror<T>(a)); } \
+    int32_t bdsp_hip_mat_to_complex##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_to_complex<T>(&a->v)); }
+
+BDSP_MAT_SYM(32, float, MatBuf32)
+BDSP_MAT_SYM(64, double, MatBuf64)
+#undef BDSP_MAT_SYM
 
 // ---------------------------------------------------------------------------------------------- B3
 int bdsp_hip_dev_fft(int elem, void* data, void* scratch, size_t points, size_t batch, unsigned flags,

@@ -189,6 +189,46 @@ class DspMat:
     def zero_pad(self, points, option=PAD_END):
         return self._call("zero_pad", int(points), int(option))
 
+    # ------------------------------------------------------------------ symmetric transforms of real rows
+    # Every row as the DspVec method of the same name on that row.  N = real points of a row, p = N // 2 + 1.  The
+    # forward forms are the batched transform plus one crop, the inverse forms one mirror launch, one 4-byte read-back
+    # (the only synchronisation) and the batched inverse transform -- whatever the number of rows.
+    def plain_sfft(self):
+        """Real time rows of odd N -> the p non-redundant bins of plain_fft per row, densely packed (complex,
+        frequency domain, delta <- N * delta).  Codes: 5 (not real / time; poisoned), 9 (N even or 0; poisoned)."""
+        return self._call("plain_sfft")
+
+    def sfft(self):
+        """As plain_sfft from the shifted spectrum fft() leaves: its first p bins, the negative half plus DC."""
+        return self._call("sfft")
+
+    def windowed_sfft(self, window):
+        """As sfft after `window` (WINDOW_*) on every row; the window is fused into the transform."""
+        return self._call("windowed_sfft", int(window))
+
+    def plain_sifft(self):
+        """Half spectra of p bins per row -> real time rows of 2p - 1 points, unnormalised (delta <- (2p - 1) * delta).
+        Codes: 6 (not complex / frequency; poisoned), 8 (the first bin of some row is not real; the whole matrix is
+        poisoned)."""
+        return self._call("plain_sifft")
+
+    def sifft(self):
+        """As plain_sifft after scaling by 1 / p and ifft_shift of every half spectrum (DspVec.sifft per row)."""
+        return self._call("sifft")
+
+    def windowed_sifft(self, window):
+        """As sifft, then every row divided by `window`."""
+        return self._call("windowed_sifft", int(window))
+
+    def mirror(self):
+        """Every row grows from p to 2p - 1 complex points: the conjugate-symmetric full spectrum of a half spectrum
+        (bit-exact).  A real time-domain matrix is poisoned (-1)."""
+        return self._call("mirror")
+
+    def to_complex(self):
+        """Every real scalar x becomes (x, 0); a complex matrix is poisoned (-1)."""
+        return self._call("to_complex")
+
     # ------------------------------------------------------------------ convolution / interpolation
     def convolve_signal(self, impulse_response):
         """One DspVec shared by all rows, or a rows x rows nested list of DspVec (MIMO:

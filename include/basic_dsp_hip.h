@@ -771,6 +771,36 @@ int32_t bdsp_hip_mat_interpolate32(MatBuf32 *m, int32_t frequency_response, floa
                                    size_t dest_points, float delay);          /* :295-307 */
 int32_t bdsp_hip_mat_interpft32(MatBuf32 *m, size_t dest_points);             /* :309-317 */
 int32_t bdsp_hip_mat_decimatei32(MatBuf32 *m, uint32_t decimation_factor, uint32_t delay); /* :319-326 */
+/* Symmetric real-signal transforms of the rows, mirror and to_complex (matrix/src/time_freq.rs:83-107
+ * SymmetricTimeToFrequencyDomainOperations, :144-168 SymmetricFrequencyToTimeDomainOperations, :173-177
+ * FrequencyDomainOperations::mirror; time_to_freq.rs:188-298, freq_to_time.rs:180-248, freq.rs:52-83 per row): every row
+ * behaves as the vector function OF THE SAME NAME on that row.  N = real points of a row, p = N/2 + 1.
+ * plain_sfft / sfft / windowed_sfft: a real time matrix with odd N becomes complex / frequency with p points per row,
+ * densely packed: the first p bins of what plain_fft / fft / windowed_fft leave (of the shifted forms: the negative half
+ * plus DC, as sfft32), delta <- N * delta.  Not real or not time: poisoned, 5; N even or rows without points: poisoned,
+ * 9; zero rows: 0, complex / frequency with no data.
+ * plain_sifft / sifft / windowed_sifft: a complex frequency matrix with p points per row becomes real / time with
+ * 2p - 1 points per row, delta <- (2p - 1) * delta; plain_sifft is unnormalised, sifft and windowed_sifft scale by 1/p
+ * (the HALF spectrum's point count, as sifft32) and rotate the half spectrum by p/2 first, windowed_sifft divides by the
+ * window last.  Not complex or not frequency: poisoned, 6.  The first bin of EVERY row (after scale and rotation) must
+ * be real: a row fails if |im0| > 1e-10 and |im0| > 1e-3 * (|re0| + |re1| + |im1|) (re1 = im1 = 0 for p == 1); if any
+ * row fails the whole matrix is poisoned, 8.  Zero rows or rows without points: 0, real / time with no data.
+ * mirror: every row grows from p to 2p - 1 complex points, out[g] = in[g] for g < p, conj(in[2p - 1 - g]) above;
+ * bit-exact; a real time-domain matrix is poisoned (-1); domain and delta stay; rows with p == 0 stay as they are (a
+ * real frequency-domain matrix is read as pairs, as mirror32 reads it: 7 for rows of an odd number of scalars).
+ * to_complex: every real scalar becomes (x, 0), rows double their length; a complex matrix is poisoned (-1).
+ * Launches, whatever the row count: the forward forms the batched transform of ONE row length plus one crop; the
+ * inverse forms one mirror launch, one 4-byte read-back of the symmetry flag (the call's only synchronisation), the
+ * batched inverse transform (+ one for windowed_sifft); mirror and to_complex one.  Memory: both device buffers of the
+ * matrix grow to rows * 2 * (2p - 1) scalars before the first launch. */
+int32_t bdsp_hip_mat_plain_sfft32(MatBuf32 *m);                            /* matrix/src/time_freq.rs:87-91 */
+int32_t bdsp_hip_mat_sfft32(MatBuf32 *m);                                  /* :93-97 */
+int32_t bdsp_hip_mat_windowed_sfft32(MatBuf32 *m, int32_t window);         /* :99-106 */
+int32_t bdsp_hip_mat_plain_sifft32(MatBuf32 *m);                           /* :148-152 */
+int32_t bdsp_hip_mat_sifft32(MatBuf32 *m);                                 /* :154-158 */
+int32_t bdsp_hip_mat_windowed_sifft32(MatBuf32 *m, int32_t window);        /* :160-167 */
+int32_t bdsp_hip_mat_mirror32(MatBuf32 *m);                                /* :173-177 */
+int32_t bdsp_hip_mat_to_complex32(MatBuf32 *m);                            /* matrix/src/real.rs:34-54 */
 
 MatBuf64 *bdsp_hip_mat_new64(int32_t is_complex, int32_t domain, size_t rows, size_t row_len, double delta); /* row_len in scalars; zero filled */
 void bdsp_hip_mat_delete64(MatBuf64 *m);
@@ -862,6 +892,15 @@ int32_t bdsp_hip_mat_interpolate64(MatBuf64 *m, int32_t frequency_response, doub
                                    size_t dest_points, double delay);
 int32_t bdsp_hip_mat_interpft64(MatBuf64 *m, size_t dest_points);
 int32_t bdsp_hip_mat_decimatei64(MatBuf64 *m, uint32_t decimation_factor, uint32_t delay);
+/* symmetric real-signal transforms of the rows, mirror, to_complex: as the f32 set above */
+int32_t bdsp_hip_mat_plain_sfft64(MatBuf64 *m);
+int32_t bdsp_hip_mat_sfft64(MatBuf64 *m);
+int32_t bdsp_hip_mat_windowed_sfft64(MatBuf64 *m, int32_t window);
+int32_t bdsp_hip_mat_plain_sifft64(MatBuf64 *m);
+int32_t bdsp_hip_mat_sifft64(MatBuf64 *m);
+int32_t bdsp_hip_mat_windowed_sifft64(MatBuf64 *m, int32_t window);
+int32_t bdsp_hip_mat_mirror64(MatBuf64 *m);
+int32_t bdsp_hip_mat_to_complex64(MatBuf64 *m);
 
 /* ==========================================================================================
  * B3 -- kernels on caller-owned DEVICE memory.  `stream` is a hipStream_t passed as void*
