@@ -312,6 +312,13 @@ for _s, _t, _R in (("32", _F, VectorInteropResult32), ("64", _D, VectorInteropRe
         _proto(_m + _n + _s, C.c_int32, _P)
     for _n in ("windowed_sfft", "windowed_sifft"):
         _proto(_m + _n + _s, C.c_int32, _P, C.c_int32)
+    # convolution with an impulse-response function, interpolation between the samples of real rows
+    _proto(_m + "convolve" + _s, C.c_int32, _P, C.c_int32, _t, _t, _SZ)
+    _proto(_m + "convolve_ex" + _s, C.c_int32, _P, C.c_int32, _t, _t, _SZ, C.c_int32)
+    _proto(_m + "convolve_real" + _s, C.c_int32, _P, _P, _P, C.c_bool, _t, _SZ)
+    _proto(_m + "convolve_complex" + _s, C.c_int32, _P, COMPLEX_FN, _P, C.c_bool, _t, _SZ)
+    for _n in ("interpolate_lin", "interpolate_hermite"):
+        _proto(_m + _n + _s, C.c_int32, _P, _t, _t)
 
 WINDOW_FN32 = C.CFUNCTYPE(_F, _P, _SZ, _SZ)
 WINDOW_FN64 = C.CFUNCTYPE(_D, _P, _SZ, _SZ)

@@ -303,6 +303,19 @@ template <typename T> int sy_crop_rows(const T* in, T* out, size_t rows, size_t 
 template <typename T>
 int sy_mirror_rows(const T* in, T* out, size_t rows, size_t p, size_t rot, bool scaled, T scale, unsigned* flag, hipStream_t s);
 
+// mat_interp.hip -- time-domain convolution with a weight table and real-row interpolation of every row of a matrix; one
+// launch each, whatever `rows`
+// out[r][i] = sum_{k=0}^{2 conv_len} in[r][(i - conv_len + k) mod points] * taps[k] for `rows` rows of `points` elements
+// (complex pairs if is_complex); taps: 2 conv_len + 1 weights in window order, (re, im) pairs if complex_taps (complex
+// rows only); conv_len <= points; out of place
+template <typename T>
+int mt_conv_direct(const T* in, T* out, size_t rows, size_t points, bool is_complex, const T* taps, size_t conv_len,
+                   bool complex_taps, hipStream_t s);
+// interpolate_real_dev for `rows` real rows of `len` scalars -> rows of interpolate_real_len(len, factor), dense, out of
+// place, bit-equal to the vector kernels
+template <typename T>
+int mt_interpolate_real(const T* in, T* out, size_t rows, size_t len, T factor, T delay, bool hermite, hipStream_t s);
+
 // bluestein.hip
 template <typename T> int bs_chirp(T* c, size_t n, bool inverse, hipStream_t s);
 template <typename T> int bs_kernel(const T* c, T* b, size_t n, size_t m, hipStream_t s);

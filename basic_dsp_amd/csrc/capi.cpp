@@ -1384,23 +1384,22 @@ int op_custom_frequency_response(DevVec<T>* v, T (*fun)(const void*, T), const v
     return ew_point_table<T>(v->data, v->valid_len, v->complex_, tb.as<T>(), false, s);
 }
 
+// the 2L + 1 weights f(-j * ratio), j = -L .. L accumulated in T as the reference does, L clipped to `points`; shared by
+// the vector and the matrix forms (one sampling for all rows)
 template <typename T>
-int op_convolve_callback(DevVec<T>* v, T (*fun)(const void*, T), const void* data, T ratio, size_t conv_len)
+std::vector<T> sample_conv_weights(T (*fun)(const void*, T), const void* data, T ratio, size_t conv_len, size_t points)
 {
-    const size_t points = v->points();
     if (conv_len > points) conv_len = points;
     std::vector<T> h(2 * conv_len + 1);
     T j = -(T)conv_len;
     for (size_t k = 0; k < h.size(); ++k) { h[k] = fun(data, -j * ratio); j = j + (T)1; }
-    return op_convolve_function<T>(v, 0, (T)0, ratio, conv_len, h.data());
+    return h;
 }
 
-// convolve_complex (convolution.rs:204-254): complex vector, complex impulse response callback
 template <typename T>
-int op_convolve_callback_complex(DevVec<T>* v, CRet<T> (*fun)(const void*, T), const void* data, T ratio, size_t conv_len)
+std::vector<T> sample_conv_weights_complex(CRet<T> (*fun)(const void*, T), const void* data, T ratio, size_t conv_len,
+                                           size_t points)
 {
-    if (!v->complex_) { v->poison(); return BDSP_OK; } // assert_complex!
-    const size_t points = v->points();
     if (conv_len > points) conv_len = points;
     std::vector<T> h(2 * (2 * conv_len + 1));
     T j = -(T)conv_len;
@@ -1409,6 +1408,22 @@ int op_convolve_callback_complex(DevVec<T>* v, CRet<T> (*fun)(const void*, T), c
         h[2 * k] = w.re; h[2 * k + 1] = w.im;
         j = j + (T)1;
     }
+    return h;
+}
+
+template <typename T>
+int op_convolve_callback(DevVec<T>* v, T (*fun)(const void*, T), const void* data, T ratio, size_t conv_len)
+{
+    const std::vector<T> h = sample_conv_weights<T>(fun, data, ratio, conv_len, v->points());
+    return op_convolve_function<T>(v, 0, (T)0, ratio, conv_len, h.data());
+}
+
+// convolve_complex (convolution.rs:204-254): complex vector, complex impulse response callback
+template <typename T>
+int op_convolve_callback_complex(DevVec<T>* v, CRet<T> (*fun)(const void*, T), const void* data, T ratio, size_t conv_len)
+{
+    if (!v->complex_) { v->poison(); return BDSP_OK; } // assert_complex!
+    const std::vector<T> h = sample_conv_weights_complex<T>(fun, data, ratio, conv_len, v->points());
     return op_convolve_function<T>(v, 0, (T)0, ratio, conv_len, h.data(), true);
 }
 
@@ -2081,6 +2096,101 @@ int mat_correlate(DevMat<T>* m, const DevVec<T>* o, size_t o_rows, size_t l, siz
     BDSP_TRY(fft_two_buffers<T>(m->v.data, m->v.buf, l, rows, true, BDSP_FFT_SHIFT_OUT, (T)1 / (T)l, -1, (T)0, &in_b, s));
     if (in_b) m->v.trade();
     return BDSP_OK; // delta is untouched
+}
+
+// host weights in window order -> the tap vector of the centred convolution: reversed, `stride` scalars per tap (real
+// weights for complex rows get zero imaginary parts), as op_convolve_function lays it out
+template <typename T>
+std::vector<T> taps_reversed(const T* host_taps, size_t ntaps, bool complex_taps, int stride)
+{
+    std::vector<T> h(ntaps * stride, (T)0);
+    for (size_t k = 0; k < ntaps; ++k) {
+        const size_t at = (ntaps - 1 - k) * stride;
+        if (complex_taps) { h[at] = host_taps[2 * k]; h[at + 1] = host_taps[2 * k + 1]; }
+        else h[at] = host_taps[k];
+    }
+    return h;
+}
+
+// convolve with an impulse-response function and interpolate_lin / interpolate_hermite of the rows
+// (matrix/src/time_freq.rs:329-387 forwards Convolution and RealInterpolationOps row by row): every row behaves as
+// op_convolve_function / op_convolve_callback / op_convolve_callback_complex / op_interpolate_real would on it.  The
+// 2L + 1 weights are tabulated once for all rows (one launch, or sampled on the host for the callback forms).
+//
+// Dispatch, ntaps = 2L + 1 with L clipped to the row's points:
+//   ntaps > points                        k_mt_conv_direct (mat_interp.hip): the window wraps around the row, which only
+//                                         the direct kernel does -- as op_convolve_function's conv_function_direct
+//   ntaps <= MAT_CONV_DIRECT_MAX_TAPS     k_mt_conv_direct: a few multiply-adds per output from LDS beat a 4096-point
+//                                         transform pair per block
+//   else                                  the reversed table is the tap vector of the centred convolution: the batched
+//                                         block kernel (conv_complex_dev / conv_real_dev with batch = rows; above
+//                                         FUSED_MAX_TAPS those run their long-filter path once per row)
+// MAT_CONV_DIRECT_MAX_TAPS is NOT MEASURED: 33 is the placeholder until tools/mat_interp_bench.py has been run on a
+// device (it times both paths at 9 .. 257 taps and names the crossover).
+constexpr size_t MAT_CONV_DIRECT_MAX_TAPS = 33;
+
+// path: -1 the dispatch above; 0 / 1 force the block convolution / the direct kernel (bdsp_hip_mat_convolve_ex, for
+// measuring the crossover: the block convolution cannot wrap around a row, 7)
+template <typename T>
+int mat_convolve_function(DevMat<T>* m, int fid, T rolloff, T ratio, size_t conv_len, const T* host_taps,
+                          bool complex_taps = false, int path = -1)
+{
+    DevVec<T>* v = &m->v;
+    if (v->freq) { v->poison(); return BDSP_OK; } // assert_time! (convolution.rs:95-102)
+    const size_t rows = m->rows, points = m->row_points();
+    if (rows == 0 || points == 0) return BDSP_OK;
+    hipStream_t s = lib_stream();
+    if (conv_len > points) conv_len = points; // mod.rs:197
+    const size_t ntaps = 2 * conv_len + 1;
+    if (path == 0 && ntaps > points) return BDSP_ERR_ARG_LENGTH;
+    const bool as_taps = path >= 0 ? path == 0 : ntaps <= points && ntaps > MAT_CONV_DIRECT_MAX_TAPS;
+    const int stride = ((as_taps && v->complex_) || complex_taps) ? 2 : 1;
+    WsBlock tb;
+    if (host_taps) {
+        std::vector<T> h(host_taps, host_taps + ntaps * (complex_taps ? 2 : 1));
+        if (as_taps) h = taps_reversed<T>(host_taps, ntaps, complex_taps, stride);
+        BDSP_TRY(upload_table<T>(tb, h, s));
+    } else {
+        BDSP_TRY(tb.alloc(sizeof(T) * ntaps * stride, s));
+        BDSP_TRY(conv_function_taps<T>(tb.as<T>(), conv_len, fid, rolloff, ratio, stride, as_taps, s));
+    }
+    if (!as_taps) BDSP_TRY(mt_conv_direct<T>(v->data, v->buf, rows, points, v->complex_, tb.as<T>(), conv_len, complex_taps, s));
+    else if (v->complex_) BDSP_TRY(conv_complex_dev<T>(v->data, v->buf, points, rows, tb.as<T>(), ntaps, s));
+    else BDSP_TRY(conv_real_dev<T>(v->data, v->buf, points, tb.as<T>(), ntaps, s, rows));
+    v->trade();
+    return BDSP_OK;
+}
+
+template <typename T>
+int mat_convolve_callback(DevMat<T>* m, T (*fun)(const void*, T), const void* data, T ratio, size_t conv_len)
+{
+    const std::vector<T> h = sample_conv_weights<T>(fun, data, ratio, conv_len, m->row_points());
+    return mat_convolve_function<T>(m, 0, (T)0, ratio, conv_len, h.data());
+}
+
+// convolve_complex (convolution.rs:204-254): complex rows, complex impulse response callback
+template <typename T>
+int mat_convolve_callback_complex(DevMat<T>* m, CRet<T> (*fun)(const void*, T), const void* data, T ratio, size_t conv_len)
+{
+    if (!m->v.complex_) { m->v.poison(); return BDSP_OK; } // assert_complex!
+    const std::vector<T> h = sample_conv_weights_complex<T>(fun, data, ratio, conv_len, m->row_points());
+    return mat_convolve_function<T>(m, 0, (T)0, ratio, conv_len, h.data(), true);
+}
+
+// rows of row_len scalars -> rows of interpolate_real_len(row_len, factor), densely packed; delta and domain stay
+template <typename T>
+int mat_interpolate_real(DevMat<T>* m, T factor, T delay, bool hermite)
+{
+    DevVec<T>* v = &m->v;
+    if (v->complex_) { v->poison(); return BDSP_OK; } // real_interpolation.rs:47-50, :89-92
+    const size_t rows = m->rows, rl = m->row_len();
+    if (rows == 0 || rl == 0) return BDSP_OK;
+    const size_t dest_len = interpolate_real_len<T>(rl, factor);
+    BDSP_TRY(v->reserve(rows * (dest_len > rl ? dest_len : rl)));
+    BDSP_TRY(mt_interpolate_real<T>(v->data, v->buf, rows, rl, factor, delay, hermite, lib_stream()));
+    v->trade();
+    v->valid_len = rows * dest_len;
+    return BDSP_OK;
 }
 
 // FFT-domain resampling and decimation of the rows (matrix/src/time_freq.rs:266-327 forwards InterpolationOps row by row):
@@ -2918,6 +3028,28 @@ BDSP_MAT_RESAMPLE(64, double, MatBuf64)
 BDSP_MAT_SYM(32, float, MatBuf32)
 BDSP_MAT_SYM(64, double, MatBuf64)
 #undef BDSP_MAT_SYM
+
+// convolve with an impulse-response function, interpolate_lin / interpolate_hermite of the rows (mat_convolve_function /
+// mat_interpolate_real above)
+#define BDSP_MAT_INTERP(SFX, T, MB)                                                                         \
+    int32_t bdsp_hip_mat_convolve##SFX(MB* m, int32_t impulse_response, T rolloff, T ratio, size_t len)     \
+    { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_convolve_function<T>(a, impulse_response == 0 ? 0 : 1, rolloff, ratio, len, nullptr)); } \
+    int32_t bdsp_hip_mat_convolve_ex##SFX(MB* m, int32_t impulse_response, T rolloff, T ratio, size_t len, int32_t path) \
+    { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_convolve_function<T>(a, impulse_response == 0 ? 0 : 1, rolloff, ratio, len, nullptr, false, path < 0 ? -1 : (path ? 1 : 0))); } \
+    int32_t bdsp_hip_mat_convolve_real##SFX(MB* m, bdsp_real_fn##SFX impulse_response, const void* impulse_response_data, \
+                                            bool, T ratio, size_t len)                                      \
+    { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_convolve_callback<T>(a, impulse_response, impulse_response_data, ratio, len)); } \
+    int32_t bdsp_hip_mat_convolve_complex##SFX(MB* m, bdsp_complex_fn##SFX impulse_response, const void* impulse_response_data, \
+                                               bool, T ratio, size_t len)                                   \
+    { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_convolve_callback_complex<T>(a, reinterpret_cast<CRet<T> (*)(const void*, T)>(impulse_response), impulse_response_data, ratio, len)); } \
+    int32_t bdsp_hip_mat_interpolate_lin##SFX(MB* m, T interpolation_factor, T delay)                       \
+    { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_interpolate_real<T>(a, interpolation_factor, delay, false)); } \
+    int32_t bdsp_hip_mat_interpolate_hermite##SFX(MB* m, T interpolation_factor, T delay)                   \
+    { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_interpolate_real<T>(a, interpolation_factor, delay, true)); }
+
+BDSP_MAT_INTERP(32, float, MatBuf32)
+BDSP_MAT_INTERP(64, double, MatBuf64)
+#undef BDSP_MAT_INTERP
 
 // ---------------------------------------------------------------------------------------------- B3
 int bdsp_hip_dev_fft(int elem, void* data, void* scratch, size_t points, size_t batch, unsigned flags,

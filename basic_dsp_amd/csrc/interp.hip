@@ -17,6 +17,7 @@
 #include <map>
 #include <mutex>
 #include "dsp_funcs.h"
+#include "mat_interp_core.h"
 #include <vector>
 
 namespace bdsp {
@@ -964,25 +965,14 @@ size_t interpolate_real_len(size_t len, T factor)
     return (size_t)(sizeof(T) == 4 ? roundf((float)v) : round((double)v)) + 1;
 }
 
-template <typename T>
-__device__ __forceinline__ T clamped(const T* __restrict__ x, long long len, long long i)
-{
-    i = i < 0 ? 0 : (i >= len ? len - 1 : i);
-    return x[i];
-}
-
+// The per-output arithmetic and the Hermite regions are in mat_interp_core.h, shared with the matrix unit
+// (mat_interp.hip), whose rows are bit-equal to these kernels' results.
 template <typename T>
 __global__ void __launch_bounds__(256)
 k_interp_lin(const T* __restrict__ in, T* __restrict__ out, long long len, long long dest_len, T factor, T delay)
 {
-    for (long long n = (long long)blockIdx.x * 256 + threadIdx.x; n < dest_len; n += (long long)gridDim.x * 256) {
-        if (n == dest_len - 1) { out[n] = in[len - 1]; continue; } // :68
-        T rounded = (T)n / factor + delay;
-        T beforef = dev_floor(rounded);
-        long long before = (long long)beforef;
-        T y0 = clamped(in, len, before), y1 = clamped(in, len, before + 1);
-        out[n] = y0 + (y1 - y0) * (rounded - beforef);
-    }
+    for (long long n = (long long)blockIdx.x * 256 + threadIdx.x; n < dest_len; n += (long long)gridDim.x * 256)
+        out[n] = interp_lin_value<T>(in, len, dest_len, n, factor, delay);
 }
 
 template <typename T>
@@ -990,31 +980,8 @@ __global__ void __launch_bounds__(256)
 k_interp_hermite(const T* __restrict__ in, T* __restrict__ out, long long len, long long dest_len, T factor, T delay,
                  long long start, long long tail)
 {
-    const T half = (T)0.5, c15 = (T)1.5, two = (T)2, c25 = (T)2.5;
-    for (long long n = (long long)blockIdx.x * 256 + threadIdx.x; n < dest_len; n += (long long)gridDim.x * 256) {
-        T rounded = (T)n / factor + delay;
-        T beforef = dev_floor(rounded);
-        long long before = (long long)beforef;
-        T x = rounded - beforef;
-        T y0, y1, y2, y3;
-        if (n < start) { // :103-124
-            y1 = clamped(in, len, before); y2 = clamped(in, len, before + 1); y3 = clamped(in, len, before + 2);
-            y0 = y1 - (y2 - y1);
-        } else if (n < tail) { // :126-145
-            y0 = clamped(in, len, before - 1); y1 = clamped(in, len, before);
-            y2 = clamped(in, len, before + 1); y3 = clamped(in, len, before + 2);
-        } else { // :147-172
-            y0 = clamped(in, len, before - 1); y1 = clamped(in, len, before);
-            y2 = (before >= 0 && before < len - 1) ? in[before + 1] : y1 + (y1 - y0);
-            y3 = (before >= 0 && before + 2 < len) ? in[before + 2] : y2 + (y2 - y1);
-        }
-        T x2 = x * x;
-        T a0 = -half * y0 + c15 * y1 - c15 * y2 + half * y3;
-        T a1 = y0 - c25 * y1 + two * y2 - half * y3;
-        T a2 = -half * y0 + half * y2;
-        T a3 = y1;
-        out[n] = (a0 * x * x2) + (a1 * x2) + (a2 * x) + a3;
-    }
+    for (long long n = (long long)blockIdx.x * 256 + threadIdx.x; n < dest_len; n += (long long)gridDim.x * 256)
+        out[n] = interp_hermite_value<T>(in, len, n, factor, delay, start, tail);
 }
 
 template <typename T>
@@ -1028,12 +995,8 @@ int interpolate_real_dev(const T* in, T* out, size_t len, T factor, T delay, boo
         hipLaunchKernelGGL((k_interp_lin<T>), dim3((unsigned)blocks), dim3(256), 0, s, in, out, (long long)len,
                            (long long)dest_len, factor, delay);
     } else {
-        T st = ((T)1 - delay) * factor;
-        double c = sizeof(T) == 4 ? (double)ceilf((float)st) : ceil((double)st);
-        long long start = c < 0 ? 0 : (long long)c, end = start + 1;
-        if (start > (long long)dest_len) start = (long long)dest_len;
-        long long tail = (long long)dest_len > end ? (long long)dest_len - end : 0;
-        if (tail < start) tail = start;
+        long long start, tail;
+        interp_hermite_regions<T>(dest_len, factor, delay, &start, &tail);
         hipLaunchKernelGGL((k_interp_hermite<T>), dim3((unsigned)blocks), dim3(256), 0, s, in, out, (long long)len,
                            (long long)dest_len, factor, delay, start, tail);
     }

@@ -259,6 +259,44 @@ class DspMat:
     def multiply_frequency_response(self, function, ratio, rolloff=0.0):
         return self._call("multiply_frequency_response", int(function), rolloff, ratio)
 
+    # ------------------------------------------------------------------ time-domain smoothing, real-row resampling
+    # Every row as the DspVec method of the same name on that row.  One launch for the weight table (none for a
+    # callable) and one for all rows while the 2 * conv_len + 1 weights are few or wrap around the row, else the batched
+    # block convolution; one launch for an interpolation -- whatever the number of rows.
+    def convolve(self, function, ratio, conv_len, rolloff=0.0):
+        """Circular convolution of every row with an impulse response sampled at 2 * conv_len + 1 points `ratio`
+        apart (conv_len is clipped to the row's points): `function` is CONV_SINC, CONV_RAISED_COSINE with `rolloff`, or a
+        Python callable f(x) the host samples once for all rows.  Delta and domain stay.  Codes: 0; -1 for a
+        frequency-domain matrix (poisoned) or one that was poisoned before; a matrix with no rows or empty rows is left
+        as it is (0)."""
+        if callable(function):
+            cb = (_lib.REAL_FN32 if self._sfx == "32" else _lib.REAL_FN64)(lambda _data, x: function(x))
+            return self._call("convolve_real", cb, None, True, ratio, int(conv_len))
+        return self._call("convolve", int(function), rolloff, ratio, int(conv_len))
+
+    def convolve_complex(self, function, ratio, conv_len):
+        """As convolve with a complex-valued Python callable f(x), complex rows only.  Codes: 0; -1 for a real or a
+        frequency-domain matrix (poisoned) or one that was poisoned before."""
+        def cb(_ctx, x, out):
+            r = complex(function(x))
+            out[0], out[1] = r.real, r.imag
+        bridge = getattr(_lib, "ComplexBridge" + self._sfx)(getattr(_lib, "COMPLEX_PTR_FN" + self._sfx)(cb), None)
+        fn = C.cast(getattr(lib, "bdsp_hip_complex_fn_bridge" + self._sfx), C.c_void_p)
+        return self._call("convolve_complex", fn, C.addressof(bridge), True, ratio, int(conv_len))
+
+    def interpolate_lin(self, interpolation_factor, delay=0.0):
+        """Every real row of n scalars resampled to round((n - 1) * interpolation_factor) + 1 scalars by linear
+        interpolation between its samples, shifted by `delay` samples; bit-equal to DspVec.interpolate_lin on the row.
+        Delta and domain stay.  Codes: 0; -1 for a complex matrix (poisoned) or one that was poisoned before; no rows or
+        empty rows: 0."""
+        return self._call("interpolate_lin", interpolation_factor, delay)
+
+    def interpolate_hermite(self, interpolation_factor, delay=0.0):
+        """As interpolate_lin with piecewise cubic Hermite (Catmull-Rom) interpolation, the end points extrapolated
+        linearly; bit-equal to DspVec.interpolate_hermite on the row.  Codes: 0; -1 for a complex matrix
+        (poisoned) or one that was poisoned before; no rows or empty rows: 0."""
+        return self._call("interpolate_hermite", interpolation_factor, delay)
+
     # ------------------------------------------------------------------ FFT-domain resampling, decimation
     # Every row as the DspVec method of the same name on that row; real rows stay real.  One launch when the new row
     # length is an integer multiple of the old one and a power of two of at most 4096 points, else a batched forward

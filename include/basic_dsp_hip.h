@@ -801,6 +801,31 @@ int32_t bdsp_hip_mat_sifft32(MatBuf32 *m);                                 /* :1
 int32_t bdsp_hip_mat_windowed_sifft32(MatBuf32 *m, int32_t window);        /* :160-167 */
 int32_t bdsp_hip_mat_mirror32(MatBuf32 *m);                                /* :173-177 */
 int32_t bdsp_hip_mat_to_complex32(MatBuf32 *m);                            /* matrix/src/real.rs:34-54 */
+/* Convolution with an impulse-response function and interpolation between the samples of real rows
+ * (matrix/src/time_freq.rs:355-387 Convolution::convolve with a real / complex function, :329-353 RealInterpolationOps;
+ * convolution.rs:136-254 and real_interpolation.rs:33-176 per row): every row behaves as the vector function OF THE SAME
+ * NAME on that row, and the arguments are the vector facade's (impulse_response 0 = sinc, anything else = raised
+ * cosine(rolloff); callbacks as bdsp_real_fn / bdsp_complex_fn, is_symmetric is accepted and not used, as there).
+ * convolve / convolve_real / convolve_complex: y[i] = sum_{k=0}^{2L} x[(i - L + k) mod N] * f(-(k - L) * ratio) per row,
+ * L = len clipped to the row's points N, accumulated over ascending k in the matrix's precision.  The callback forms
+ * sample the 2L + 1 weights on the host ONCE for all rows.  A frequency-domain matrix is poisoned (-1) by every form, a
+ * real matrix by convolve_complex; zero rows or empty rows: 0, matrix as it is; delta and domain stay.
+ * interpolate_lin / interpolate_hermite: real rows of n scalars become rows of round((n - 1) * factor) + 1 scalars,
+ * densely packed, bit-equal to interpolate_lin32/64 and interpolate_hermite32/64 on the row; a complex matrix is
+ * poisoned (-1); zero rows or empty rows: 0; delta and domain stay.
+ * Launches, whatever the row count: the interpolations one; convolve one for the weight table (none for the callback
+ * forms) plus one direct kernel when 2L + 1 exceeds N or is at most 33 taps, else the batched block convolution
+ * bdsp_hip_mat_convolve_signal uses.  Memory: the interpolations grow both device buffers of the matrix to
+ * rows * max(old, new row length) scalars before the launch. */
+int32_t bdsp_hip_mat_convolve32(MatBuf32 *m, int32_t impulse_response, float rolloff, float ratio, size_t len); /* matrix/src/time_freq.rs:355-370 */
+int32_t bdsp_hip_mat_convolve_ex32(MatBuf32 *m, int32_t impulse_response, float rolloff, float ratio, size_t len,
+                                   int32_t path); /* path < 0: as bdsp_hip_mat_convolve; 0: the block convolution whatever the tap count (7 if 2L + 1 exceeds the row's points); else: the direct kernel.  For measuring the crossover. */
+int32_t bdsp_hip_mat_convolve_real32(MatBuf32 *m, bdsp_real_fn32 impulse_response, const void *impulse_response_data,
+                                     bool is_symmetric, float ratio, size_t len);                   /* :355-370 */
+int32_t bdsp_hip_mat_convolve_complex32(MatBuf32 *m, bdsp_complex_fn32 impulse_response, const void *impulse_response_data,
+                                        bool is_symmetric, float ratio, size_t len);                /* :372-387 */
+int32_t bdsp_hip_mat_interpolate_lin32(MatBuf32 *m, float interpolation_factor, float delay);     /* :343-352 */
+int32_t bdsp_hip_mat_interpolate_hermite32(MatBuf32 *m, float interpolation_factor, float delay); /* :333-342 */
 
 MatBuf64 *bdsp_hip_mat_new64(int32_t is_complex, int32_t domain, size_t rows, size_t row_len, double delta); /* row_len in scalars; zero filled */
 void bdsp_hip_mat_delete64(MatBuf64 *m);
@@ -901,6 +926,15 @@ int32_t bdsp_hip_mat_sifft64(MatBuf64 *m);
 int32_t bdsp_hip_mat_windowed_sifft64(MatBuf64 *m, int32_t window);
 int32_t bdsp_hip_mat_mirror64(MatBuf64 *m);
 int32_t bdsp_hip_mat_to_complex64(MatBuf64 *m);
+int32_t bdsp_hip_mat_convolve64(MatBuf64 *m, int32_t impulse_response, double rolloff, double ratio, size_t len); /* matrix/src/time_freq.rs:355-370 */
+int32_t bdsp_hip_mat_convolve_ex64(MatBuf64 *m, int32_t impulse_response, double rolloff, double ratio, size_t len,
+                                   int32_t path); /* path < 0: as bdsp_hip_mat_convolve; 0: the block convolution whatever the tap count (7 if 2L + 1 exceeds the row's points); else: the direct kernel.  For measuring the crossover. */
+int32_t bdsp_hip_mat_convolve_real64(MatBuf64 *m, bdsp_real_fn64 impulse_response, const void *impulse_response_data,
+                                     bool is_symmetric, double ratio, size_t len);                   /* :355-370 */
+int32_t bdsp_hip_mat_convolve_complex64(MatBuf64 *m, bdsp_complex_fn64 impulse_response, const void *impulse_response_data,
+                                        bool is_symmetric, double ratio, size_t len);                /* :372-387 */
+int32_t bdsp_hip_mat_interpolate_lin64(MatBuf64 *m, double interpolation_factor, double delay);     /* :343-352 */
+int32_t bdsp_hip_mat_interpolate_hermite64(MatBuf64 *m, double interpolation_factor, double delay); /* :333-342 */
 
 /* ==========================================================================================
  * B3 -- kernels on caller-owned DEVICE memory.  `stream` is a hipStream_t passed as void*
