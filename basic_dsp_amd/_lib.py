@@ -319,6 +319,19 @@ for _s, _t, _R in (("32", _F, VectorInteropResult32), ("64", _D, VectorInteropRe
     _proto(_m + "convolve_complex" + _s, C.c_int32, _P, COMPLEX_FN, _P, C.c_bool, _t, _SZ)
     for _n in ("interpolate_lin", "interpolate_hermite"):
         _proto(_m + _n + _s, C.c_int32, _P, _t, _t)
+    # math family, reverse, mixer, *_smaller and part operations of the rows
+    for _n in ("sqrt", "square", "ln", "exp", "sin", "cos", "tan", "asin", "acos", "atan", "sinh", "cosh", "tanh",
+               "asinh", "acosh", "atanh", "abs", "ln_approx", "exp_approx", "sin_approx", "cos_approx", "reverse"):
+        _proto(_m + _n + _s, C.c_int32, _P)
+    for _n in ("root", "powf", "log", "expf", "log_approx", "expf_approx", "powf_approx"):
+        _proto(_m + _n + _s, C.c_int32, _P, _t)
+    _proto(_m + "multiply_complex_exponential" + _s, C.c_int32, _P, _t, _t)
+    for _n in ("add_smaller", "sub_smaller", "mul_smaller", "div_smaller", "add_smaller_vector", "sub_smaller_vector",
+               "mul_smaller_vector", "div_smaller_vector", "get_real", "get_imag", "get_magnitude",
+               "get_magnitude_squared", "get_phase"):
+        _proto(_m + _n + _s, C.c_int32, _P, _P)
+    for _n in ("get_real_imag", "get_mag_phase", "set_real_imag", "set_mag_phase"):
+        _proto(_m + _n + _s, C.c_int32, _P, _P, _P)
 
 WINDOW_FN32 = C.CFUNCTYPE(_F, _P, _SZ, _SZ)
 WINDOW_FN64 = C.CFUNCTYPE(_D, _P, _SZ, _SZ)

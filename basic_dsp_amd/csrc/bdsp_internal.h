@@ -316,6 +316,17 @@ int mt_conv_direct(const T* in, T* out, size_t rows, size_t points, bool is_comp
 template <typename T>
 int mt_interpolate_real(const T* in, T* out, size_t rows, size_t len, T factor, T delay, bool hermite, hipStream_t s);
 
+// mat_ew.hip -- the row-aware elementwise operations of a matrix; one launch each, whatever `rows`
+// z[r][k] *= exp(j (a k + b)) for `rows` rows of `points` complex points, k from 0 in every row; in place
+template <typename T> int mw_cexp(T* x, size_t rows, size_t points, double a, double b, hipStream_t s);
+// out[r][i] = in[r][points - 1 - i] in elements (complex pairs if is_complex); out of place
+template <typename T> int mw_reverse(const T* in, T* out, size_t rows, size_t points, bool is_complex, hipStream_t s);
+// x[r][i] (.)= y[r * ystride + i mod ypoints] in elements, op 0 .. 3 = add, sub, mul, div (ew_binary_smaller's
+// expressions); ystride 0: one operand for every row; ypoints must divide points (else BDSP_ERR_ARG_LENGTH); in place
+template <typename T>
+int mw_smaller(T* x, const T* y, size_t rows, size_t points, size_t ypoints, size_t ystride, bool is_complex, int op,
+               hipStream_t s);
+
 // bluestein.hip
 template <typename T> int bs_chirp(T* c, size_t n, bool inverse, hipStream_t s);
 template <typename T> int bs_kernel(const T* c, T* b, size_t n, size_t m, hipStream_t s);

@@ -2365,6 +2365,102 @@ int mat_mirror(DevMat<T>* m)
     return BDSP_OK;
 }
 
+// Math family, reverse, mixer, *_smaller and part operations of the rows (mat_ew.hip; matrix/src/general/elementary.rs
+// :117-350, real.rs:58-130, complex.rs:119-211): every row as the vector function of the same name on it.  The math
+// family is op_math on the flat vector (the arithmetic does not look at the position); the getters and setters are the
+// flat ew_complex_to_real / vm_complex_split / vm_complex_join over rows * points; reverse, the mixer and *_smaller
+// know the rows.  One launch each, whatever the row count.
+template <typename T>
+int mat_reverse(DevMat<T>* m)
+{
+    const size_t p = m->row_points();
+    if (m->rows == 0 || p == 0) return BDSP_OK;
+    BDSP_TRY(mw_reverse<T>(m->v.data, m->v.buf, m->rows, p, m->v.complex_, lib_stream()));
+    m->v.trade();
+    return BDSP_OK;
+}
+
+template <typename T>
+int mat_mul_cexp(DevMat<T>* m, T a, T b)
+{
+    if (!m->v.complex_) { m->v.poison(); return BDSP_OK; } // assert_complex!, complex_ops.rs:81-83
+    // a * delta and b * delta are formed in T first, as multiply_complex_exponential32/64 form them
+    return mw_cexp<T>(m->v.data, m->rows, m->row_points(), (double)(a * m->v.delta), (double)(b * m->v.delta), lib_stream());
+}
+
+// row r wraps around row r of `o`
+template <typename T>
+int mat_smaller(DevMat<T>* m, const DevMat<T>* o, int op)
+{
+    if (o->rows != m->rows) return BDSP_ERR_ARG_LENGTH; // as mat_binary
+    if (m->rows == 0) return BDSP_OK;                   // no rows: neither side has a row length to check
+    const size_t rl = m->row_len(), yl = o->row_len(), e = m->v.complex_ ? 2 : 1;
+    if (yl == 0 || rl % yl != 0) return BDSP_ERR_ARG_LENGTH; // elementary.rs:613-617, per row
+    if (!meta_agrees(&m->v, &o->v)) return BDSP_ERR_META_DATA;
+    return mw_smaller<T>(m->v.data, o->v.data, m->rows, rl / e, yl / e, yl / e, m->v.complex_, op, lib_stream());
+}
+
+// every row wraps around the same vector: its length must divide the ROW length, not the allocation's
+template <typename T>
+int mat_smaller_vector(DevMat<T>* m, const DevVec<T>* o, int op)
+{
+    const size_t rl = m->row_len(), yl = o->valid_len, e = m->v.complex_ ? 2 : 1;
+    if (yl == 0 || rl % yl != 0) return BDSP_ERR_ARG_LENGTH;
+    if (!meta_agrees(&m->v, o)) return BDSP_ERR_META_DATA;
+    return mw_smaller<T>(m->v.data, o->data, m->rows, rl / e, yl / e, 0, m->v.complex_, op, lib_stream());
+}
+
+// get_real / get_imag / get_magnitude / get_magnitude_squared / get_phase (kind as op_get_complex_to_real): `dst`
+// becomes m->rows rows of `points` reals and keeps its delta and domain; a real source or a complex destination leaves
+// it with m->rows empty rows.  The source is not consumed.
+template <typename T>
+int mat_get_part(const DevMat<T>* m, DevMat<T>* dst, int kind)
+{
+    if (m->v.erroneous()) return BDSP_ERR_POISONED;
+    size_t total = 0;
+    if (m->v.complex_ && !dst->v.complex_) {
+        total = m->rows * m->row_points();
+        BDSP_TRY(dst->v.reserve(total ? total : 1));
+        BDSP_TRY(ew_complex_to_real<T>(m->v.data, dst->v.data, m->v.valid_len, kind, lib_stream()));
+    }
+    dst->rows = m->rows;
+    dst->v.valid_len = total;
+    return BDSP_OK;
+}
+
+// get_real_imag (kind 0) / get_mag_phase (kind 1), as op_get_pair
+template <typename T>
+int mat_get_pair(const DevMat<T>* m, DevMat<T>* a, DevMat<T>* b, int kind)
+{
+    if (m->v.erroneous()) return BDSP_ERR_POISONED;
+    size_t total = 0;
+    if (m->v.complex_ && !a->v.complex_ && !b->v.complex_) {
+        total = m->rows * m->row_points();
+        BDSP_TRY(a->v.reserve(total ? total : 1));
+        BDSP_TRY(b->v.reserve(total ? total : 1));
+        BDSP_TRY(vm_complex_split<T>(m->v.data, a->v.data, b->v.data, total, kind, lib_stream()));
+    }
+    a->rows = m->rows; b->rows = m->rows;
+    a->v.valid_len = total; b->v.valid_len = total;
+    return BDSP_OK;
+}
+
+// set_real_imag (kind 0) / set_mag_phase (kind 1), as op_set_pair: m becomes complex with the shape of `a`
+template <typename T>
+int mat_set_pair(DevMat<T>* m, const DevMat<T>* a, const DevMat<T>* b, int kind)
+{
+    if (a->rows != b->rows || a->v.valid_len != b->v.valid_len) return BDSP_ERR_ARG_LENGTH;
+    if (m->v.erroneous()) return BDSP_OK; // stays poisoned
+    if (a == m || b == m) { set_last_error("set_real_imag / set_mag_phase: an argument is the target itself"); return BDSP_ERR_UNSUPPORTED; }
+    const size_t total = a->v.valid_len;
+    BDSP_TRY(m->v.reserve(total ? 2 * total : 1));
+    BDSP_TRY(vm_complex_join<T>(m->v.data, a->v.data, b->v.data, total, kind, lib_stream()));
+    m->v.complex_ = true;
+    m->rows = a->rows;
+    m->v.valid_len = 2 * total;
+    return BDSP_OK;
+}
+
 } // namespace
 
 // ==============================================================================================
@@ -3050,6 +3146,66 @@ BDSP_MAT_SYM(64, double, MatBuf64)
 BDSP_MAT_INTERP(32, float, MatBuf32)
 BDSP_MAT_INTERP(64, double, MatBuf64)
 #undef BDSP_MAT_INTERP
+
+// math family, reverse, mixer, *_smaller and part operations of the rows (op_math and mat_reverse .. mat_set_pair above)
+#define BDSP_MAT_EW_M0(SFX, T, MB, NAME, FN, REAL_ONLY)                                                     \
+    int32_t bdsp_hip_mat_##NAME##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_math<T>(&a->v, FN, (T)0, REAL_ONLY)); }
+#define BDSP_MAT_EW_M1(SFX, T, MB, NAME, FN, REAL_ONLY)                                                     \
+    int32_t bdsp_hip_mat_##NAME##SFX(MB* m, T value) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_math<T>(&a->v, FN, value, REAL_ONLY)); }
+#define BDSP_MAT_EW(SFX, T, MB, VB)                                                                         \
+    BDSP_MAT_EW_M0(SFX, T, MB, sqrt, MATH_SQRT, false)                                                      \
+    BDSP_MAT_EW_M0(SFX, T, MB, square, MATH_SQUARE, false)                                                  \
+    BDSP_MAT_EW_M0(SFX, T, MB, ln, MATH_LN, false)                                                          \
+    BDSP_MAT_EW_M0(SFX, T, MB, exp, MATH_EXP, false)                                                        \
+    BDSP_MAT_EW_M0(SFX, T, MB, sin, MATH_SIN, false)                                                        \
+    BDSP_MAT_EW_M0(SFX, T, MB, cos, MATH_COS, false)                                                        \
+    BDSP_MAT_EW_M0(SFX, T, MB, tan, MATH_TAN, false)                                                        \
+    BDSP_MAT_EW_M0(SFX, T, MB, asin, MATH_ASIN, false)                                                      \
+    BDSP_MAT_EW_M0(SFX, T, MB, acos, MATH_ACOS, false)                                                      \
+    BDSP_MAT_EW_M0(SFX, T, MB, atan, MATH_ATAN, false)                                                      \
+    BDSP_MAT_EW_M0(SFX, T, MB, sinh, MATH_SINH, false)                                                      \
+    BDSP_MAT_EW_M0(SFX, T, MB, cosh, MATH_COSH, false)                                                      \
+    BDSP_MAT_EW_M0(SFX, T, MB, tanh, MATH_TANH, false)                                                      \
+    BDSP_MAT_EW_M0(SFX, T, MB, asinh, MATH_ASINH, false)                                                    \
+    BDSP_MAT_EW_M0(SFX, T, MB, acosh, MATH_ACOSH, false)                                                    \
+    BDSP_MAT_EW_M0(SFX, T, MB, atanh, MATH_ATANH, false)                                                    \
+    BDSP_MAT_EW_M0(SFX, T, MB, abs, MATH_ABS, true)                                                         \
+    BDSP_MAT_EW_M0(SFX, T, MB, ln_approx, MATH_LN, true)                                                    \
+    BDSP_MAT_EW_M0(SFX, T, MB, exp_approx, MATH_EXP, true)                                                  \
+    BDSP_MAT_EW_M0(SFX, T, MB, sin_approx, MATH_SIN, true)                                                  \
+    BDSP_MAT_EW_M0(SFX, T, MB, cos_approx, MATH_COS, true)                                                  \
+    BDSP_MAT_EW_M1(SFX, T, MB, powf, MATH_POWF, false)                                                      \
+    BDSP_MAT_EW_M1(SFX, T, MB, log, MATH_LOG, false)                                                        \
+    BDSP_MAT_EW_M1(SFX, T, MB, expf, MATH_EXPF, false)                                                      \
+    BDSP_MAT_EW_M1(SFX, T, MB, log_approx, MATH_LOG, true)                                                  \
+    BDSP_MAT_EW_M1(SFX, T, MB, expf_approx, MATH_EXPF_APPROX, true)                                         \
+    BDSP_MAT_EW_M1(SFX, T, MB, powf_approx, MATH_POWF_APPROX, true)                                         \
+    int32_t bdsp_hip_mat_root##SFX(MB* m, T value) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_math<T>(&a->v, MATH_POWF, (T)1 / value, false)); } /* powf(1 / degree), as root32 */ \
+    int32_t bdsp_hip_mat_reverse##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_reverse<T>(a)); } \
+    int32_t bdsp_hip_mat_multiply_complex_exponential##SFX(MB* m, T a, T b) { DevMat<T>* x = M##SFX(m); return mat_code<T>(x, mat_mul_cexp<T>(x, a, b)); } \
+    int32_t bdsp_hip_mat_add_smaller##SFX(MB* m, const MB* o) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_smaller<T>(a, MC##SFX(o), 0)); } \
+    int32_t bdsp_hip_mat_sub_smaller##SFX(MB* m, const MB* o) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_smaller<T>(a, MC##SFX(o), 1)); } \
+    int32_t bdsp_hip_mat_mul_smaller##SFX(MB* m, const MB* o) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_smaller<T>(a, MC##SFX(o), 2)); } \
+    int32_t bdsp_hip_mat_div_smaller##SFX(MB* m, const MB* o) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_smaller<T>(a, MC##SFX(o), 3)); } \
+    int32_t bdsp_hip_mat_add_smaller_vector##SFX(MB* m, const VB* o) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_smaller_vector<T>(a, H<T>(o), 0)); } \
+    int32_t bdsp_hip_mat_sub_smaller_vector##SFX(MB* m, const VB* o) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_smaller_vector<T>(a, H<T>(o), 1)); } \
+    int32_t bdsp_hip_mat_mul_smaller_vector##SFX(MB* m, const VB* o) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_smaller_vector<T>(a, H<T>(o), 2)); } \
+    int32_t bdsp_hip_mat_div_smaller_vector##SFX(MB* m, const VB* o) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_smaller_vector<T>(a, H<T>(o), 3)); } \
+    int32_t bdsp_hip_mat_get_real##SFX(const MB* m, MB* destination) { return mat_get_part<T>(MC##SFX(m), M##SFX(destination), 2); } \
+    int32_t bdsp_hip_mat_get_imag##SFX(const MB* m, MB* destination) { return mat_get_part<T>(MC##SFX(m), M##SFX(destination), 3); } \
+    int32_t bdsp_hip_mat_get_magnitude##SFX(const MB* m, MB* destination) { return mat_get_part<T>(MC##SFX(m), M##SFX(destination), 0); } \
+    int32_t bdsp_hip_mat_get_magnitude_squared##SFX(const MB* m, MB* destination) { return mat_get_part<T>(MC##SFX(m), M##SFX(destination), 1); } \
+    int32_t bdsp_hip_mat_get_phase##SFX(const MB* m, MB* destination) { return mat_get_part<T>(MC##SFX(m), M##SFX(destination), 4); } \
+    int32_t bdsp_hip_mat_get_real_imag##SFX(const MB* m, MB* real, MB* imag) { return mat_get_pair<T>(MC##SFX(m), M##SFX(real), M##SFX(imag), 0); } \
+    int32_t bdsp_hip_mat_get_mag_phase##SFX(const MB* m, MB* mag, MB* phase) { return mat_get_pair<T>(MC##SFX(m), M##SFX(mag), M##SFX(phase), 1); } \
+    int32_t bdsp_hip_mat_set_real_imag##SFX(MB* m, const MB* real, const MB* imag) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_set_pair<T>(a, MC##SFX(real), MC##SFX(imag), 0)); } \
+    int32_t bdsp_hip_mat_set_mag_phase##SFX(MB* m, const MB* mag, const MB* phase) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_set_pair<T>(a, MC##SFX(mag), MC##SFX(phase), 1)); }
+
+BDSP_MAT_EW(32, float, MatBuf32, VecBuf32)
+BDSP_MAT_EW(64, double, MatBuf64, VecBuf64)
+#undef BDSP_MAT_EW
+#undef BDSP_MAT_EW_M0
+#undef BDSP_MAT_EW_M1
 
 // ---------------------------------------------------------------------------------------------- B3
 int bdsp_hip_dev_fft(int elem, void* data, void* scratch, size_t points, size_t batch, unsigned flags,

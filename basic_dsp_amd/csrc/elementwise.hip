@@ -6,6 +6,7 @@
 #include "bdsp_internal.h"
 #include "dsp_funcs.h"
 #include "ew_map.h"
+#include "mat_ew_core.h"
 
 namespace bdsp {
 
@@ -62,13 +63,10 @@ template <typename T> struct OpMulCexp {
     struct Params { double a, b; };
     static __device__ __forceinline__ void apply(T* e, int n, size_t i0, Params p)
     {
-        for (int i = 0; i + 1 < n; i += 2) {
-            double k = (double)((i0 + i) / 2);
-            double s, c;
-            sincos(p.a * k + p.b, &s, &c);
-            T wr = (T)c, wi = (T)s, zr = e[i], zi = e[i + 1];
-            e[i] = zr * wr - zi * wi;
-            e[i + 1] = zr * wi + zi * wr;
+        for (int i = 0; i + 1 < n; i += 2) { // the expressions are in mat_ew_core.h, shared with the matrix unit
+            T wr, wi;
+            cexp_phasor<T>(p.a, p.b, (double)((i0 + i) / 2), &wr, &wi);
+            cexp_mul<T>(&e[i], &e[i + 1], wr, wi);
         }
     }
 };
@@ -346,17 +344,12 @@ __global__ __launch_bounds__(256) void k_binary_smaller(T* __restrict__ x, const
 {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < points; i += (size_t)gridDim.x * blockDim.x) {
         size_t j = i % ypoints;
-        if (CPLX) {
-            T ar = x[2 * i], ai = x[2 * i + 1], br = y[2 * j], bi = y[2 * j + 1];
+        if (CPLX) { // the four expressions are in mat_ew_core.h, shared with the matrix unit
             T re, im;
-            if (op == 0) { re = ar + br; im = ai + bi; }
-            else if (op == 1) { re = ar - br; im = ai - bi; }
-            else if (op == 2) { re = ar * br - ai * bi; im = ar * bi + ai * br; }
-            else { T nn = br * br + bi * bi; re = (ar * br + ai * bi) / nn; im = (ai * br - ar * bi) / nn; }
+            smaller_complex<T>(x[2 * i], x[2 * i + 1], y[2 * j], y[2 * j + 1], op, &re, &im);
             x[2 * i] = re; x[2 * i + 1] = im;
         } else {
-            T a = x[i], b = y[j];
-            x[i] = op == 0 ? a + b : (op == 1 ? a - b : (op == 2 ? a * b : a / b));
+            x[i] = smaller_real<T>(x[i], y[j], op);
         }
     }
 }

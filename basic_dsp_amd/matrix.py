@@ -152,6 +152,105 @@ class DspMat:
         """Undoes wrap along every row (divisor 2 pi for a phase); a complex matrix is poisoned (-1)."""
         return self._call("unwrap", divisor)
 
+    # ------------------------------------------------------------------ math family, reverse, mixer, *_smaller, parts
+    # Every row as the DspVec method of the same name on that row, bit for bit; one launch each, whatever the number of
+    # rows, and no synchronisation.
+    def _math0(name, real_only):  # noqa: N805 -- method factory
+        def method(self):
+            return self._call(name)
+        method.__name__ = name
+        method.__doc__ = "`%s` of every element in place, as DspVec.%s on every row.  Codes: 0; -1 for a %smatrix that " \
+            "was poisoned before; no rows or empty rows: 0." % (name, name, "complex matrix (poisoned) or a " if real_only else "")
+        return method
+
+    def _math1(name, real_only):  # noqa: N805
+        def method(self, value):
+            return self._call(name, value)
+        method.__name__ = name
+        method.__doc__ = "`%s(value)` of every element in place, as DspVec.%s on every row.  Codes: 0; -1 for a %smatrix " \
+            "that was poisoned before; no rows or empty rows: 0." % (name, name, "complex matrix (poisoned) or a " if real_only else "")
+        return method
+
+    for _n in ("sqrt", "square", "ln", "exp", "sin", "cos", "tan", "asin", "acos", "atan", "sinh", "cosh", "tanh",
+               "asinh", "acosh", "atanh"):
+        locals()[_n] = _math0(_n, False)
+    for _n in ("abs", "ln_approx", "exp_approx", "sin_approx", "cos_approx"):
+        locals()[_n] = _math0(_n, True)
+    for _n in ("powf", "root", "log", "expf"):
+        locals()[_n] = _math1(_n, False)
+    for _n in ("log_approx", "expf_approx", "powf_approx"):
+        locals()[_n] = _math1(_n, True)
+    del _n, _math0, _math1
+
+    def reverse(self):
+        """Every row back to front: row[i] <- row[points - 1 - i], bit-exact; the order of the rows, delta and domain
+        stay.  Codes: 0; -1 for a matrix that was poisoned before; no rows or empty rows: 0."""
+        return self._call("reverse")
+
+    def multiply_complex_exponential(self, a, b):
+        """z[r][k] *= exp(j (a * delta * k + b * delta)) with k counted from 0 in every row: mixes every row by the same
+        frequency.  The phasor of a position is computed once and reused down the rows.  Codes: 0; -1 for a real matrix
+        (poisoned) or one that was poisoned before; no rows or empty rows: 0."""
+        return self._call("multiply_complex_exponential", a, b)
+
+    def add_smaller(self, other):
+        """row[i] += operand[i mod len(operand)]: row r wraps around row r of a DspMat, or every row around one DspVec.
+        Codes: 0; 7 if the row counts differ, the operand('s rows) are empty or their length does not divide the ROW
+        length; 2 if number space, domain or delta disagree; -1 for a matrix that was poisoned before.  The matrix is
+        untouched after an error."""
+        return self._binary("add_smaller", other)
+
+    def sub_smaller(self, other):
+        """row[i] -= operand[i mod len(operand)].  Codes: as add_smaller (0, 7, 2, -1)."""
+        return self._binary("sub_smaller", other)
+
+    def mul_smaller(self, other):
+        """row[i] *= operand[i mod len(operand)].  Codes: as add_smaller (0, 7, 2, -1)."""
+        return self._binary("mul_smaller", other)
+
+    def div_smaller(self, other):
+        """row[i] /= operand[i mod len(operand)].  Codes: as add_smaller (0, 7, 2, -1)."""
+        return self._binary("div_smaller", other)
+
+    def get_real(self, destination):
+        """The real parts into the DspMat `destination`, which becomes rows x points real scalars and keeps its delta;
+        self stays as it is.  A real self or a complex destination leaves `destination` with rows() empty rows.  Codes: 0;
+        -1 if self is poisoned (destination untouched)."""
+        return self._call("get_real", destination._h)
+
+    def get_imag(self, destination):
+        """The imaginary parts into `destination`.  Codes and shapes: as get_real (0, -1)."""
+        return self._call("get_imag", destination._h)
+
+    def get_magnitude(self, destination):
+        """|z| of every point into `destination`.  Codes and shapes: as get_real (0, -1)."""
+        return self._call("get_magnitude", destination._h)
+
+    def get_magnitude_squared(self, destination):
+        """re^2 + im^2 of every point into `destination`.  Codes and shapes: as get_real (0, -1)."""
+        return self._call("get_magnitude_squared", destination._h)
+
+    def get_phase(self, destination):
+        """atan2(im, re) of every point into `destination`.  Codes and shapes: as get_real (0, -1)."""
+        return self._call("get_phase", destination._h)
+
+    def get_real_imag(self, real, imag):
+        """Real and imaginary parts into two DspMat in one pass.  Codes and shapes: as get_real (0, -1)."""
+        return self._call("get_real_imag", real._h, imag._h)
+
+    def get_mag_phase(self, mag, phase):
+        """Magnitude and phase into two DspMat in one pass.  Codes and shapes: as get_real (0, -1)."""
+        return self._call("get_mag_phase", mag._h, phase._h)
+
+    def set_real_imag(self, real, imag):
+        """self becomes complex with the shape of `real`: z = real + j imag.  Codes: 0; 7 unless both arguments have the
+        same row count and row length; -1 for a matrix that was poisoned before."""
+        return self._call("set_real_imag", real._h, imag._h)
+
+    def set_mag_phase(self, mag, phase):
+        """self becomes complex with the shape of `mag`: z = mag * exp(j phase).  Codes: as set_real_imag (0, 7, -1)."""
+        return self._call("set_mag_phase", mag._h, phase._h)
+
     # ------------------------------------------------------------------ transforms, windows, index moves
     def plain_fft(self):
         return self._call("plain_fft")

@@ -826,6 +826,81 @@ int32_t bdsp_hip_mat_convolve_complex32(MatBuf32 *m, bdsp_complex_fn32 impulse_r
                                         bool is_symmetric, float ratio, size_t len);                /* :372-387 */
 int32_t bdsp_hip_mat_interpolate_lin32(MatBuf32 *m, float interpolation_factor, float delay);     /* :343-352 */
 int32_t bdsp_hip_mat_interpolate_hermite32(MatBuf32 *m, float interpolation_factor, float delay); /* :333-342 */
+/* Math family, reverse, mixer, wrap-around binary operations and the part getters / setters of the rows
+ * (matrix/src/general/elementary.rs:226-350 TrigOps / PowerOps, real.rs:58-130 RealOps / ApproximatedOps,
+ * general/elementary.rs:190-198 ReorganizeDataOps::reverse, complex.rs:203-211 multiply_complex_exponential,
+ * general/elementary.rs:117-188 ElementaryWrapAroundOps, complex.rs:119-201 getters and setters): every row behaves as
+ * the vector function OF THE SAME NAME on that row, bit for bit.
+ * sqrt .. atanh, root, powf, log, expf: real and complex matrices; root(d) is powf(1 / d), as root32.  abs and the
+ * *_approx functions poison a complex matrix (-1).
+ * reverse: out[r][i] = in[r][points - 1 - i], bit-exact, real or complex; domain and delta stay.
+ * multiply_complex_exponential(a, b): z[r][k] *= exp(j (a delta k + b delta)) with k counted from 0 in EVERY row; a * delta
+ * and b * delta are formed in the matrix's precision, the phase in double, the phasor rounded to the matrix's precision
+ * (as multiply_complex_exponential32/64); a real matrix is poisoned (-1).
+ * add / sub / mul / div_smaller: x[r][i] (.)= y[r][i mod ypoints], row r around row r of `other`: 7 if the row counts
+ * differ, then 7 if other's rows are empty or their length does not divide the row length of m, then the meta data check
+ * of bdsp_hip_mat_add (2); two matrices without rows: 0.  *_smaller_vector: one period for all rows; the operand's
+ * length must divide the ROW length (2 rows of 3 scalars and a 2-scalar operand: 7, although 6 % 2 == 0), 7 also for an
+ * empty operand.  The matrix is untouched after an error.
+ * get_real / get_imag / get_magnitude / get_magnitude_squared / get_phase, get_real_imag / get_mag_phase: the source is
+ * NOT consumed (the vector facade consumes it and answers 9; that is a link-compatibility artefact there).  Every
+ * destination becomes rows(m) rows of `points` real scalars and keeps its own domain and delta; a real source or a
+ * complex destination leaves the destination(s) with rows(m) rows of length 0.  0; -1 if the source is poisoned, the
+ * destinations untouched.  (The reference's matrix get_magnitude, get_magnitude_squared and get_phase all forward to
+ * v.get_imag, complex.rs:135-151: a slip there, not reproduced, like diff_with_start above.)
+ * set_real_imag / set_mag_phase: 7 unless the two arguments have equal row counts and row lengths; m becomes complex
+ * with the shape of the first argument, delta and domain stay; set_mag_phase builds mag * (cos phase, sin phase).
+ * Everywhere: zero rows or empty rows: 0, no launch; a poisoned matrix: -1; an argument error (7) comes before the
+ * poison check.  Launches: ONE per call, whatever the row count, no synchronisation.  Memory: reverse writes the
+ * matrix's second buffer and trades; the getters grow the destinations' buffers to rows * points scalars, the setters
+ * the matrix's to rows * 2 * points; everything else works in place. */
+int32_t bdsp_hip_mat_sqrt32(MatBuf32 *m);  /* matrix/src/general/elementary.rs:302-350 PowerOps */
+int32_t bdsp_hip_mat_square32(MatBuf32 *m);
+int32_t bdsp_hip_mat_ln32(MatBuf32 *m);
+int32_t bdsp_hip_mat_exp32(MatBuf32 *m);
+int32_t bdsp_hip_mat_sin32(MatBuf32 *m);  /* :226-300 TrigOps */
+int32_t bdsp_hip_mat_cos32(MatBuf32 *m);
+int32_t bdsp_hip_mat_tan32(MatBuf32 *m);
+int32_t bdsp_hip_mat_asin32(MatBuf32 *m);
+int32_t bdsp_hip_mat_acos32(MatBuf32 *m);
+int32_t bdsp_hip_mat_atan32(MatBuf32 *m);
+int32_t bdsp_hip_mat_sinh32(MatBuf32 *m);
+int32_t bdsp_hip_mat_cosh32(MatBuf32 *m);
+int32_t bdsp_hip_mat_tanh32(MatBuf32 *m);
+int32_t bdsp_hip_mat_asinh32(MatBuf32 *m);
+int32_t bdsp_hip_mat_acosh32(MatBuf32 *m);
+int32_t bdsp_hip_mat_atanh32(MatBuf32 *m);
+int32_t bdsp_hip_mat_abs32(MatBuf32 *m);  /* matrix/src/real.rs:58-76 */
+int32_t bdsp_hip_mat_ln_approx32(MatBuf32 *m);  /* :78-130 */
+int32_t bdsp_hip_mat_exp_approx32(MatBuf32 *m);
+int32_t bdsp_hip_mat_sin_approx32(MatBuf32 *m);
+int32_t bdsp_hip_mat_cos_approx32(MatBuf32 *m);
+int32_t bdsp_hip_mat_root32(MatBuf32 *m, float value);
+int32_t bdsp_hip_mat_powf32(MatBuf32 *m, float value);
+int32_t bdsp_hip_mat_log32(MatBuf32 *m, float value);
+int32_t bdsp_hip_mat_expf32(MatBuf32 *m, float value);
+int32_t bdsp_hip_mat_log_approx32(MatBuf32 *m, float value);
+int32_t bdsp_hip_mat_expf_approx32(MatBuf32 *m, float value);
+int32_t bdsp_hip_mat_powf_approx32(MatBuf32 *m, float value);
+int32_t bdsp_hip_mat_reverse32(MatBuf32 *m);  /* matrix/src/general/elementary.rs:190-198 */
+int32_t bdsp_hip_mat_multiply_complex_exponential32(MatBuf32 *m, float a, float b);  /* matrix/src/complex.rs:203-211 */
+int32_t bdsp_hip_mat_add_smaller32(MatBuf32 *m, const MatBuf32 *other);  /* matrix/src/general/elementary.rs:117-188, row r around row r */
+int32_t bdsp_hip_mat_sub_smaller32(MatBuf32 *m, const MatBuf32 *other);
+int32_t bdsp_hip_mat_mul_smaller32(MatBuf32 *m, const MatBuf32 *other);
+int32_t bdsp_hip_mat_div_smaller32(MatBuf32 *m, const MatBuf32 *other);
+int32_t bdsp_hip_mat_add_smaller_vector32(MatBuf32 *m, const VecBuf32 *operand);  /* every row around the same vector */
+int32_t bdsp_hip_mat_sub_smaller_vector32(MatBuf32 *m, const VecBuf32 *operand);
+int32_t bdsp_hip_mat_mul_smaller_vector32(MatBuf32 *m, const VecBuf32 *operand);
+int32_t bdsp_hip_mat_div_smaller_vector32(MatBuf32 *m, const VecBuf32 *operand);
+int32_t bdsp_hip_mat_get_real32(const MatBuf32 *m, MatBuf32 *destination);  /* matrix/src/complex.rs:119-151 */
+int32_t bdsp_hip_mat_get_imag32(const MatBuf32 *m, MatBuf32 *destination);
+int32_t bdsp_hip_mat_get_magnitude32(const MatBuf32 *m, MatBuf32 *destination);
+int32_t bdsp_hip_mat_get_magnitude_squared32(const MatBuf32 *m, MatBuf32 *destination);
+int32_t bdsp_hip_mat_get_phase32(const MatBuf32 *m, MatBuf32 *destination);
+int32_t bdsp_hip_mat_get_real_imag32(const MatBuf32 *m, MatBuf32 *real, MatBuf32 *imag);  /* :153-175 */
+int32_t bdsp_hip_mat_get_mag_phase32(const MatBuf32 *m, MatBuf32 *mag, MatBuf32 *phase);
+int32_t bdsp_hip_mat_set_real_imag32(MatBuf32 *m, const MatBuf32 *real, const MatBuf32 *imag);  /* :177-201 */
+int32_t bdsp_hip_mat_set_mag_phase32(MatBuf32 *m, const MatBuf32 *mag, const MatBuf32 *phase);
 
 MatBuf64 *bdsp_hip_mat_new64(int32_t is_complex, int32_t domain, size_t rows, size_t row_len, double delta); /* row_len in scalars; zero filled */
 void bdsp_hip_mat_delete64(MatBuf64 *m);
@@ -935,6 +1010,54 @@ int32_t bdsp_hip_mat_convolve_complex64(MatBuf64 *m, bdsp_complex_fn64 impulse_r
                                         bool is_symmetric, double ratio, size_t len);                /* :372-387 */
 int32_t bdsp_hip_mat_interpolate_lin64(MatBuf64 *m, double interpolation_factor, double delay);     /* :343-352 */
 int32_t bdsp_hip_mat_interpolate_hermite64(MatBuf64 *m, double interpolation_factor, double delay); /* :333-342 */
+/* math family, reverse, mixer, *_smaller and part operations of the rows: as the f32 set above */
+int32_t bdsp_hip_mat_sqrt64(MatBuf64 *m);
+int32_t bdsp_hip_mat_square64(MatBuf64 *m);
+int32_t bdsp_hip_mat_ln64(MatBuf64 *m);
+int32_t bdsp_hip_mat_exp64(MatBuf64 *m);
+int32_t bdsp_hip_mat_sin64(MatBuf64 *m);
+int32_t bdsp_hip_mat_cos64(MatBuf64 *m);
+int32_t bdsp_hip_mat_tan64(MatBuf64 *m);
+int32_t bdsp_hip_mat_asin64(MatBuf64 *m);
+int32_t bdsp_hip_mat_acos64(MatBuf64 *m);
+int32_t bdsp_hip_mat_atan64(MatBuf64 *m);
+int32_t bdsp_hip_mat_sinh64(MatBuf64 *m);
+int32_t bdsp_hip_mat_cosh64(MatBuf64 *m);
+int32_t bdsp_hip_mat_tanh64(MatBuf64 *m);
+int32_t bdsp_hip_mat_asinh64(MatBuf64 *m);
+int32_t bdsp_hip_mat_acosh64(MatBuf64 *m);
+int32_t bdsp_hip_mat_atanh64(MatBuf64 *m);
+int32_t bdsp_hip_mat_abs64(MatBuf64 *m);
+int32_t bdsp_hip_mat_ln_approx64(MatBuf64 *m);
+int32_t bdsp_hip_mat_exp_approx64(MatBuf64 *m);
+int32_t bdsp_hip_mat_sin_approx64(MatBuf64 *m);
+int32_t bdsp_hip_mat_cos_approx64(MatBuf64 *m);
+int32_t bdsp_hip_mat_root64(MatBuf64 *m, double value);
+int32_t bdsp_hip_mat_powf64(MatBuf64 *m, double value);
+int32_t bdsp_hip_mat_log64(MatBuf64 *m, double value);
+int32_t bdsp_hip_mat_expf64(MatBuf64 *m, double value);
+int32_t bdsp_hip_mat_log_approx64(MatBuf64 *m, double value);
+int32_t bdsp_hip_mat_expf_approx64(MatBuf64 *m, double value);
+int32_t bdsp_hip_mat_powf_approx64(MatBuf64 *m, double value);
+int32_t bdsp_hip_mat_reverse64(MatBuf64 *m);
+int32_t bdsp_hip_mat_multiply_complex_exponential64(MatBuf64 *m, double a, double b);
+int32_t bdsp_hip_mat_add_smaller64(MatBuf64 *m, const MatBuf64 *other);
+int32_t bdsp_hip_mat_sub_smaller64(MatBuf64 *m, const MatBuf64 *other);
+int32_t bdsp_hip_mat_mul_smaller64(MatBuf64 *m, const MatBuf64 *other);
+int32_t bdsp_hip_mat_div_smaller64(MatBuf64 *m, const MatBuf64 *other);
+int32_t bdsp_hip_mat_add_smaller_vector64(MatBuf64 *m, const VecBuf64 *operand);
+int32_t bdsp_hip_mat_sub_smaller_vector64(MatBuf64 *m, const VecBuf64 *operand);
+int32_t bdsp_hip_mat_mul_smaller_vector64(MatBuf64 *m, const VecBuf64 *operand);
+int32_t bdsp_hip_mat_div_smaller_vector64(MatBuf64 *m, const VecBuf64 *operand);
+int32_t bdsp_hip_mat_get_real64(const MatBuf64 *m, MatBuf64 *destination);
+int32_t bdsp_hip_mat_get_imag64(const MatBuf64 *m, MatBuf64 *destination);
+int32_t bdsp_hip_mat_get_magnitude64(const MatBuf64 *m, MatBuf64 *destination);
+int32_t bdsp_hip_mat_get_magnitude_squared64(const MatBuf64 *m, MatBuf64 *destination);
+int32_t bdsp_hip_mat_get_phase64(const MatBuf64 *m, MatBuf64 *destination);
+int32_t bdsp_hip_mat_get_real_imag64(const MatBuf64 *m, MatBuf64 *real, MatBuf64 *imag);
+int32_t bdsp_hip_mat_get_mag_phase64(const MatBuf64 *m, MatBuf64 *mag, MatBuf64 *phase);
+int32_t bdsp_hip_mat_set_real_imag64(MatBuf64 *m, const MatBuf64 *real, const MatBuf64 *imag);
+int32_t bdsp_hip_mat_set_mag_phase64(MatBuf64 *m, const MatBuf64 *mag, const MatBuf64 *phase);
 
 /* ==========================================================================================
  * B3 -- kernels on caller-owned DEVICE memory.  `stream` is a hipStream_t passed as void*
