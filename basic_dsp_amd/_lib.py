@@ -332,6 +332,10 @@ for _s, _t, _R in (("32", _F, VectorInteropResult32), ("64", _D, VectorInteropRe
         _proto(_m + _n + _s, C.c_int32, _P, _P)
     for _n in ("get_real_imag", "get_mag_phase", "set_real_imag", "set_mag_phase"):
         _proto(_m + _n + _s, C.c_int32, _P, _P, _P)
+    # vector <-> matrix: the result handle comes back through the last argument
+    _proto(_m + "from_frames" + _s, C.c_int32, _P, _SZ, _SZ, C.c_int32, C.POINTER(_P))
+    _proto(_m + "overlap_add" + _s, C.c_int32, _P, _SZ, C.POINTER(_P))
+    _proto(_m + "from_vectors" + _s, C.c_int32, C.POINTER(_P), _SZ, C.POINTER(_P))
 
 WINDOW_FN32 = C.CFUNCTYPE(_F, _P, _SZ, _SZ)
 WINDOW_FN64 = C.CFUNCTYPE(_D, _P, _SZ, _SZ)

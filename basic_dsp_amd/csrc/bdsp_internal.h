@@ -327,6 +327,26 @@ template <typename T>
 int mw_smaller(T* x, const T* y, size_t rows, size_t points, size_t ypoints, size_t ystride, bool is_complex, int op,
                hipStream_t s);
 
+// mat_frame.hip -- vector <-> matrix moves and the index moves of the rows; one launch each, whatever `rows`; sizes in
+// elements (complex pairs if is_complex), everything out of place, bit-exact
+// out[r][j] = x[r * hop + j], zero at or past `points`; out: rows x frame_points
+template <typename T>
+int mf_from_frames(const T* x, T* out, size_t points, size_t rows, size_t frame_points, size_t hop, bool is_complex,
+                   hipStream_t s);
+// y[i] = sum of m[r][i - r * hop] over the rows that reach i, ascending r, from +0; y: (rows - 1) * hop + frame_points
+template <typename T>
+int mf_overlap_add(const T* m, T* y, size_t rows, size_t frame_points, size_t hop, bool is_complex, hipStream_t s);
+// out[r] = vectors[r] (a DEVICE table of `rows` device pointers to `points` elements each)
+template <typename T>
+int mf_from_vectors(const T* const* vectors, T* out, size_t rows, size_t points, bool is_complex, hipStream_t s);
+// every row as rg_zero_pad (option 0 End, 1 Surround, else Center); BDSP_ERR_ARG_LENGTH unless points > points_before
+template <typename T>
+int mf_zero_pad(const T* in, T* out, size_t rows, size_t points_before, size_t points, bool is_complex, int option,
+                hipStream_t s);
+// every row as rg_rotate: out[r][i] = in[r][(i + shift) mod points]
+template <typename T>
+int mf_rotate(const T* in, T* out, size_t rows, size_t points, size_t shift, bool is_complex, hipStream_t s);
+
 // bluestein.hip
 template <typename T> int bs_chirp(T* c, size_t n, bool inverse, hipStream_t s);
 template <typename T> int bs_kernel(const T* c, T* b, size_t n, size_t m, hipStream_t s);

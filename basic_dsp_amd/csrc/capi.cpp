@@ -11,11 +11,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
 
 #include "bdsp_internal.h"
+#include "mat_frame_core.h"
 
 using namespace bdsp;
 
@@ -1738,7 +1740,7 @@ int dot(const DevVec<T>* v, const DevVec<T>* o, bool cplx, double* re, double* i
 // ----------------------------------------------------------------------------------------------
 // Matrix / batch API: `rows` equally long vectors back to back in ONE allocation; a row may start at any
 // scalar, so nothing here may assume a 16-byte aligned row.  Operations are batched launches over all rows
-// except the ones that go through mat_resize_rows and the MIMO convolution (one launch per row).  Mirrors
+// except interpolatef (through mat_resize_rows) and the MIMO convolution (one launch per row).  Mirrors
 // the matrix crate (matrix/src/lib.rs:195-208 applies an operation to the rows one after the other;
 // matrix/src/time_freq.rs:49-530 forwards the time/frequency traits row by row) -- here the row loop is
 // the grid's batch dimension.
@@ -1819,10 +1821,13 @@ int mat_window(DevMat<T>* m, int window, bool unapply)
 template <typename T>
 int mat_swap(DevMat<T>* m, bool forward)
 {
-    const size_t p = m->row_points(), e = m->v.complex_ ? 2 : 1;
+    const size_t p = m->row_points();
     if (p == 0) return BDSP_OK;
     const size_t shift = forward ? p - p / 2 : p / 2;
-    return mat_resize_rows<T>(m, m->row_len(), [&](const T* in, T* out) { return rg_rotate<T>(in, out, p, e, shift, lib_stream()); });
+    // one launch over rows x points: every row as rg_rotate on it
+    BDSP_TRY(mf_rotate<T>(m->v.data, m->v.buf, m->rows, p, shift, m->v.complex_, lib_stream()));
+    m->v.trade();
+    return BDSP_OK;
 }
 
 template <typename T>
@@ -1832,8 +1837,106 @@ int mat_zero_pad(DevMat<T>* m, size_t points, int option)
     if (len <= rl) return BDSP_ERR_ARG_LENGTH; // an argument error comes first, as in every other call
     if (m->v.erroneous()) return BDSP_OK; // a poisoned matrix stays poisoned: padding its empty rows would hide the error
     const int opt = option == 0 ? 0 : (option == 1 ? 1 : 2);
-    const bool c = m->v.complex_;
-    return mat_resize_rows<T>(m, len, [&](const T* in, T* out) { return rg_zero_pad<T>(in, out, rl, c, points, opt, lib_stream()); });
+    // one launch over rows x points: every row as rg_zero_pad on it
+    BDSP_TRY(m->v.reserve(m->rows * len));
+    BDSP_TRY(mf_zero_pad<T>(m->v.data, m->v.buf, m->rows, rl / step, points, m->v.complex_, opt, lib_stream()));
+    m->v.trade();
+    m->v.valid_len = m->rows * len;
+    return BDSP_OK;
+}
+
+// Vector <-> matrix (mat_frame.hip).  from_frames and overlap_add are the analysis and synthesis steps of an STFT on a
+// signal that stays in HBM; from_vectors is the reference's to_mat (matrix/src/to_from_mat_conversions.rs).  Each
+// allocates its result and launches once, whatever the row count.  The result handle is *out (null after an argument
+// error or a failed allocation); a poisoned source gives a poisoned result and BDSP_ERR_POISONED.
+static bool mat_extent(size_t a, size_t b, size_t add, size_t elem, size_t* scalars)
+{
+    size_t t;
+    if (__builtin_mul_overflow(a, b, &t) || __builtin_add_overflow(t, add, &t) || __builtin_mul_overflow(t, elem, &t) ||
+        t > (size_t(1) << 60)) {
+        set_last_error("the result's length does not fit the address space");
+        return false;
+    }
+    *scalars = t;
+    return true;
+}
+
+template <typename T>
+void meta_copy(DevVec<T>* to, const DevVec<T>* from)
+{
+    to->complex_ = from->complex_;
+    to->freq = from->freq;
+    to->delta = from->delta;
+}
+
+// row r = x[r * hop .. r * hop + frame_points), zero past the end; the row counts are mf_frame_rows's
+template <typename T>
+int mat_from_frames(const DevVec<T>* v, size_t frame_points, size_t hop, bool pad_tail, DevMat<T>** out)
+{
+    *out = nullptr;
+    if (frame_points == 0 || hop == 0) return BDSP_ERR_ARG_LENGTH;
+    const size_t e = v->complex_ ? 2 : 1, rows = mf_frame_rows(v->points(), frame_points, hop, pad_tail);
+    size_t total;
+    if (!mat_extent(rows, frame_points, 0, e, &total)) return BDSP_ERR_UNSUPPORTED;
+    std::unique_ptr<DevMat<T>> m(new DevMat<T>());
+    meta_copy<T>(&m->v, v); // a poisoned source: no points, so no rows, and its NaN delta poisons the result
+    m->rows = rows;
+    BDSP_TRY(m->v.reserve(total ? total : 1));
+    BDSP_TRY(mf_from_frames<T>(v->data, m->v.data, v->points(), rows, frame_points, hop, v->complex_, lib_stream()));
+    m->v.valid_len = total;
+    *out = m.release();
+    return (*out)->v.erroneous() ? BDSP_ERR_POISONED : BDSP_OK;
+}
+
+// y[i] = sum over r, ascending, of m[r][i - r * hop]: (rows - 1) * hop + row points
+template <typename T>
+int mat_overlap_add(const DevMat<T>* m, size_t hop, DevVec<T>** out)
+{
+    *out = nullptr;
+    if (hop == 0) return BDSP_ERR_ARG_LENGTH;
+    const size_t e = m->v.complex_ ? 2 : 1, rows = m->rows, p = m->row_points();
+    size_t total = 0;
+    if (rows && !m->v.erroneous() && !mat_extent(rows - 1, hop, p, e, &total)) return BDSP_ERR_UNSUPPORTED;
+    std::unique_ptr<DevVec<T>> y(new DevVec<T>());
+    meta_copy<T>(y.get(), &m->v);
+    BDSP_TRY(y->reserve(total ? total : 1));
+    BDSP_TRY(mf_overlap_add<T>(m->v.data, y->data, total ? rows : 0, p, hop, m->v.complex_, lib_stream()));
+    y->valid_len = total;
+    *out = y.release();
+    return (*out)->erroneous() ? BDSP_ERR_POISONED : BDSP_OK;
+}
+
+// row r = a copy of vectors[r]; number space, domain and delta are the first vector's
+template <typename T>
+int mat_from_vectors(const DevVec<T>* const* vectors, size_t count, DevMat<T>** out)
+{
+    *out = nullptr;
+    std::unique_ptr<DevMat<T>> m(new DevMat<T>());
+    bool poisoned = false, lengths = true, meta = true;
+    for (size_t k = 0; k < count; ++k) {
+        poisoned = poisoned || vectors[k]->erroneous();
+        lengths = lengths && vectors[k]->valid_len == vectors[0]->valid_len;
+        meta = meta && vectors[k]->complex_ == vectors[0]->complex_ && vectors[k]->freq == vectors[0]->freq;
+    }
+    if (count) meta_copy<T>(&m->v, vectors[0]);
+    m->rows = count;
+    size_t total = 0;
+    if (poisoned) m->v.poison(); // count empty rows
+    else if (!lengths) return BDSP_ERR_ARG_LENGTH;
+    else if (!meta) return BDSP_ERR_META_DATA;
+    else if (count && !mat_extent(count, vectors[0]->valid_len, 0, 1, &total)) return BDSP_ERR_UNSUPPORTED;
+    BDSP_TRY(m->v.reserve(total ? total : 1));
+    if (total) {
+        // one table of `count` device pointers, one launch (upload_parts waits for the table's copy: the call's only
+        // synchronisation)
+        hipStream_t s = lib_stream();
+        WsBlock tb;
+        BDSP_TRY(upload_parts<T>(tb, const_cast<DevVec<T>* const*>(vectors), count, s));
+        BDSP_TRY(mf_from_vectors<T>(tb.as<const T*>(), m->v.data, count, vectors[0]->points(), m->v.complex_, s));
+    }
+    m->v.valid_len = total;
+    *out = m.release();
+    return poisoned ? BDSP_ERR_POISONED : BDSP_OK;
 }
 
 // convolve_signal with ONE impulse response shared by all rows (matrix/src/time_freq.rs:421-431)
@@ -3206,6 +3309,20 @@ BDSP_MAT_EW(64, double, MatBuf64, VecBuf64)
 #undef BDSP_MAT_EW
 #undef BDSP_MAT_EW_M0
 #undef BDSP_MAT_EW_M1
+
+// vector <-> matrix: frames of a vector, overlap-add of the rows, rows from vectors (mat_from_frames .. mat_from_vectors
+// above)
+#define BDSP_MAT_FRAME(SFX, T, MB, VB)                                                                      \
+    int32_t bdsp_hip_mat_from_frames##SFX(const VB* vector, size_t frame_points, size_t hop, int32_t pad_tail, MB** out) \
+    { DevMat<T>* m = nullptr; const int c = mat_from_frames<T>(H<T>(vector), frame_points, hop, pad_tail != 0, &m); *out = reinterpret_cast<MB*>(m); return c; } \
+    int32_t bdsp_hip_mat_overlap_add##SFX(const MB* m, size_t hop, VB** out)                                \
+    { DevVec<T>* y = nullptr; const int c = mat_overlap_add<T>(MC##SFX(m), hop, &y); *out = reinterpret_cast<VB*>(y); return c; } \
+    int32_t bdsp_hip_mat_from_vectors##SFX(const VB* const* vectors, size_t count, MB** out)                \
+    { DevMat<T>* m = nullptr; const int c = mat_from_vectors<T>(reinterpret_cast<const DevVec<T>* const*>(vectors), count, &m); *out = reinterpret_cast<MB*>(m); return c; }
+
+BDSP_MAT_FRAME(32, float, MatBuf32, VecBuf32)
+BDSP_MAT_FRAME(64, double, MatBuf64, VecBuf64)
+#undef BDSP_MAT_FRAME
 
 // ---------------------------------------------------------------------------------------------- B3
 int bdsp_hip_dev_fft(int elem, void* data, void* scratch, size_t points, size_t batch, unsigned flags,

@@ -14,7 +14,11 @@ from .vector import DspVec, TIME, PAD_END
 
 class DspMat:
     def __init__(self, rows_data=None, is_complex=False, domain=TIME, delta=1.0, dtype=np.float32,
-                 rows=None, row_len=None):
+                 rows=None, row_len=None, _handle=None, _sfx=None):
+        if _handle is not None:
+            self._h, self._sfx = _handle, _sfx
+            self.dtype = np.float32 if _sfx == "32" else np.float64
+            return
         _lib.require_gpu()
         if rows_data is not None:
             a = np.ascontiguousarray(rows_data)
@@ -84,6 +88,52 @@ class DspMat:
 
     def set_row(self, row, vector):
         return self._call("set_row", int(row), vector._h)
+
+    # ------------------------------------------------------------------ vector <-> matrix
+    # A signal that lives in HBM becomes a batch and a batch becomes a signal again without a host round trip: one
+    # launch each, whatever the number of rows.  All three allocate their result, so none can be captured into a Graph.
+    @classmethod
+    def from_frames(cls, vector, frame_points, hop, pad_tail=False):
+        """(code, DspMat-or-None): the overlapping frames of the DspVec `vector` as rows -- row r, point j is
+        x[r * hop + j], positions past the end read as zero (frame_points and hop in points; the analysis step of an
+        STFT).  Rows: (points - frame_points) // hop + 1 whole frames (none if the vector is shorter than a frame); with
+        pad_tail a last, zero-extended frame covers the tail, ceil((points - frame_points) / hop) + 1 (one row for a
+        vector no longer than a frame, none for an empty one).  Number space, domain and delta are the vector's, which
+        stays as it is.  Bit-exact.  Codes: 0; 7 if frame_points or hop is 0 (no matrix); -1 for a poisoned vector (the
+        matrix is poisoned too).  Allocates, so it cannot be captured into a Graph."""
+        out = C.c_void_p()
+        fn = getattr(lib, "bdsp_hip_mat_from_frames" + vector._sfx)
+        code = _lib.check(fn(vector._h, int(frame_points), int(hop), int(bool(pad_tail)), C.byref(out)),
+                          "mat_from_frames" + vector._sfx)
+        return code, (cls(_handle=out.value, _sfx=vector._sfx) if out.value else None)
+
+    @classmethod
+    def from_vectors(cls, vectors, dtype=np.float32):
+        """(code, DspMat-or-None): row r is a copy of the DspVec vectors[r] (the reference's to_mat); number space,
+        domain and delta are the first vector's.  One pointer-table upload and one launch, however many vectors.  An
+        empty list gives a real matrix of `dtype` without rows.  Codes: 0; -1 if any vector is poisoned (the matrix is
+        poisoned too); 7 for unequal lengths, 2 for unequal number space or domain (no matrix).  Allocates, so it cannot be
+        captured into a Graph."""
+        vectors = list(vectors)
+        sfx = vectors[0]._sfx if vectors else ("32" if np.dtype(dtype).type == np.float32 else "64")
+        assert all(v._sfx == sfx for v in vectors), "vectors of one precision"
+        out = C.c_void_p()
+        arr = (C.c_void_p * max(len(vectors), 1))(*[v._h for v in vectors])
+        code = _lib.check(getattr(lib, "bdsp_hip_mat_from_vectors" + sfx)(arr, len(vectors), C.byref(out)),
+                          "mat_from_vectors" + sfx)
+        return code, (cls(_handle=out.value, _sfx=sfx) if out.value else None)
+
+    def overlap_add(self, hop):
+        """(code, DspVec-or-None): the rows summed into one vector, row r starting at point r * hop -- (rows - 1) * hop +
+        row_points() points, y[i] = sum of row r's point i - r * hop over the rows that reach i (the synthesis step of an
+        STFT).  A gather without atomics: the terms are added in ascending r from +0, so the result is deterministic and
+        bit-equal to the row loop y[r * hop : r * hop + F] += m[r] in the matrix's dtype.  hop > row_points() leaves zero
+        gaps, hop == row_points() flattens the matrix.  Number space, domain and delta are the matrix's, which stays as it
+        is.  Codes: 0 (a matrix without rows gives an empty vector); 7 if hop is 0 (no vector); -1 for a poisoned matrix
+        (the vector is poisoned too).  Allocates, so it cannot be captured into a Graph."""
+        out = C.c_void_p()
+        code = _lib.check(self._fn("overlap_add")(self._h, int(hop), C.byref(out)), "mat_overlap_add" + self._sfx)
+        return code, (DspVec(_handle=out.value, _sfx=self._sfx) if out.value else None)
 
     # ------------------------------------------------------------------ elementwise
     def scale(self, factor):
@@ -276,6 +326,7 @@ class DspMat:
     def unapply_window(self, window):
         return self._call("unapply_window", int(window))
 
+    # the four index moves below are one launch over rows x row points each, every row as the DspVec method on it
     def swap_halves(self):
         return self._call("swap_halves")
 

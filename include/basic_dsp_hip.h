@@ -901,6 +901,30 @@ int32_t bdsp_hip_mat_get_real_imag32(const MatBuf32 *m, MatBuf32 *real, MatBuf32
 int32_t bdsp_hip_mat_get_mag_phase32(const MatBuf32 *m, MatBuf32 *mag, MatBuf32 *phase);
 int32_t bdsp_hip_mat_set_real_imag32(MatBuf32 *m, const MatBuf32 *real, const MatBuf32 *imag);  /* :177-201 */
 int32_t bdsp_hip_mat_set_mag_phase32(MatBuf32 *m, const MatBuf32 *mag, const MatBuf32 *phase);
+/* Vector <-> matrix without a host round trip (the reference builds matrices from vectors with to_mat,
+ * matrix/src/to_from_mat_conversions.rs; from_frames and overlap_add are the analysis and synthesis steps of an STFT on
+ * a signal that stays in HBM).  P, F, H in POINTS (a complex point is two scalars).  Each call allocates its result,
+ * hands it back through *out (to be deleted by the caller with bdsp_hip_mat_delete / delete_vector) and launches ONCE,
+ * whatever the row count; because they allocate, none of them can be captured into a graph.  All three are bit-exact.
+ * from_frames(vector, F, H, pad_tail): row r, point j = x[r * H + j]; positions at or past P read as zero.  Rows:
+ * pad_tail == 0: P >= F ? (P - F) / H + 1 : 0 (whole frames only); otherwise P == 0 ? 0 : (P > F ? ceil((P - F) / H) + 1
+ * : 1) (every point lies in a frame, the last one zero-extended).  Number space, domain and delta are the vector's, which
+ * stays as it is.  F == 0 or H == 0: 7, *out = NULL.
+ * overlap_add(m, H): a vector of rows ? (rows - 1) * H + F : 0 points, y[i] = sum of m[r][i - r * H] over the rows with
+ * 0 <= i - r * H < F, added in ascending r from +0 by the one lane that owns y[i] -- no atomics, so deterministic and
+ * bit-equal to the row loop y[r * H .. r * H + F) += m[r] in the matrix's precision.  H > F leaves zero gaps, H == F
+ * flattens the matrix.  Number space, domain and delta are the matrix's, which stays as it is.  H == 0: 7, *out = NULL;
+ * a matrix without rows: an empty vector, 0.
+ * from_vectors(vectors, count): row r = a copy of vectors[r]; number space, domain and delta of vectors[0].  count == 0:
+ * a real time-domain matrix without rows, 0.  Any poisoned vector: a poisoned matrix, -1; else unequal lengths: 7;
+ * else unequal number space or domain: 2 (*out = NULL after 7 and 2).  One upload of the pointer table (the call's only
+ * synchronisation) and one launch, whatever `count`.  The other direction is bdsp_hip_mat_get_row, or
+ * overlap_add(H = row points) for the flat vector.
+ * Everywhere: a poisoned source gives a poisoned result (no rows or points, NaN delta) and -1; a failed allocation or a
+ * result too long for the address space returns the backend code (<= -100) with *out = NULL. */
+int32_t bdsp_hip_mat_from_frames32(const VecBuf32 *vector, size_t frame_points, size_t hop, int32_t pad_tail, MatBuf32 **out);
+int32_t bdsp_hip_mat_overlap_add32(const MatBuf32 *m, size_t hop, VecBuf32 **out);
+int32_t bdsp_hip_mat_from_vectors32(const VecBuf32 *const *vectors, size_t count, MatBuf32 **out);
 
 MatBuf64 *bdsp_hip_mat_new64(int32_t is_complex, int32_t domain, size_t rows, size_t row_len, double delta); /* row_len in scalars; zero filled */
 void bdsp_hip_mat_delete64(MatBuf64 *m);
@@ -1058,6 +1082,10 @@ int32_t bdsp_hip_mat_get_real_imag64(const MatBuf64 *m, MatBuf64 *real, MatBuf64
 int32_t bdsp_hip_mat_get_mag_phase64(const MatBuf64 *m, MatBuf64 *mag, MatBuf64 *phase);
 int32_t bdsp_hip_mat_set_real_imag64(MatBuf64 *m, const MatBuf64 *real, const MatBuf64 *imag);
 int32_t bdsp_hip_mat_set_mag_phase64(MatBuf64 *m, const MatBuf64 *mag, const MatBuf64 *phase);
+/* vector <-> matrix (matrix/src/to_from_mat_conversions.rs): see bdsp_hip_mat_from_frames32 */
+int32_t bdsp_hip_mat_from_frames64(const VecBuf64 *vector, size_t frame_points, size_t hop, int32_t pad_tail, MatBuf64 **out);
+int32_t bdsp_hip_mat_overlap_add64(const MatBuf64 *m, size_t hop, VecBuf64 **out);
+int32_t bdsp_hip_mat_from_vectors64(const VecBuf64 *const *vectors, size_t count, MatBuf64 **out);
 
 /* ==========================================================================================
  * B3 -- kernels on caller-owned DEVICE memory.  `stream` is a hipStream_t passed as void*
