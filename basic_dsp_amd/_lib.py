@@ -336,6 +336,11 @@ for _s, _t, _R in (("32", _F, VectorInteropResult32), ("64", _D, VectorInteropRe
     _proto(_m + "from_frames" + _s, C.c_int32, _P, _SZ, _SZ, C.c_int32, C.POINTER(_P))
     _proto(_m + "overlap_add" + _s, C.c_int32, _P, _SZ, C.POINTER(_P))
     _proto(_m + "from_vectors" + _s, C.c_int32, C.POINTER(_P), _SZ, C.POINTER(_P))
+    # across the rows: transpose, interleaved channels <-> rows, zero interleave
+    _proto(_m + "transpose" + _s, C.c_int32, _P)
+    _proto(_m + "from_interleaved" + _s, C.c_int32, _P, _SZ, C.POINTER(_P))
+    _proto(_m + "to_interleaved" + _s, C.c_int32, _P, C.POINTER(_P))
+    _proto(_m + "zero_interleave" + _s, C.c_int32, _P, C.c_int32)
 
 WINDOW_FN32 = C.CFUNCTYPE(_F, _P, _SZ, _SZ)
 WINDOW_FN64 = C.CFUNCTYPE(_D, _P, _SZ, _SZ)

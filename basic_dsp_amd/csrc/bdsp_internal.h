@@ -347,6 +347,11 @@ int mf_zero_pad(const T* in, T* out, size_t rows, size_t points_before, size_t p
 template <typename T>
 int mf_rotate(const T* in, T* out, size_t rows, size_t points, size_t shift, bool is_complex, hipStream_t s);
 
+// mat_transpose.hip -- src: R rows of C elements (complex pairs if is_complex) -> dst: C rows of R elements, out of place
+// (BDSP_ERR_UNSUPPORTED if src == dst), bit-exact, one launch; a row may start at any element
+template <typename T>
+int tp_transpose(const T* src, T* dst, size_t R, size_t C, bool is_complex, hipStream_t s);
+
 // bluestein.hip
 template <typename T> int bs_chirp(T* c, size_t n, bool inverse, hipStream_t s);
 template <typename T> int bs_kernel(const T* c, T* b, size_t n, size_t m, hipStream_t s);

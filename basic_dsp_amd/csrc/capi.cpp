@@ -1939,6 +1939,73 @@ int mat_from_vectors(const DevVec<T>* const* vectors, size_t count, DevMat<T>** 
     return poisoned ? BDSP_ERR_POISONED : BDSP_OK;
 }
 
+// Across the rows (mat_transpose.hip): one tiled transpose of whole elements serves transpose, from_interleaved and
+// to_interleaved (the reference's split_into and merge, data_reorganization.rs:477-555, with the rows of one matrix as
+// targets and sources); one launch each, no pointer table, no synchronisation.
+// In place through the trade buffer, as mat_swap: rows <- the old row points, the scalar count stays, so nothing is
+// allocated.  An empty matrix loses its rows; a poisoned one is left alone (mat_code answers -1).
+template <typename T>
+int mat_transpose(DevMat<T>* m)
+{
+    if (m->v.erroneous()) return BDSP_OK;
+    const size_t rows = m->rows, p = m->row_points();
+    if (rows == 0 || p == 0) { m->rows = 0; m->v.valid_len = 0; return BDSP_OK; }
+    BDSP_TRY(m->v.reserve(m->v.valid_len)); // both buffers hold valid_len scalars already: no allocation
+    BDSP_TRY(tp_transpose<T>(m->v.data, m->v.buf, rows, p, m->v.complex_, lib_stream()));
+    m->v.trade();
+    m->rows = p;
+    return BDSP_OK;
+}
+
+// row c, point j = x[j * channels + c]: the transpose of the vector seen as [points / channels][channels]
+template <typename T>
+int mat_from_interleaved(const DevVec<T>* v, size_t channels, DevMat<T>** out)
+{
+    *out = nullptr;
+    if (channels == 0 || v->points() % channels != 0) return BDSP_ERR_ARG_LENGTH; // data_reorganization.rs:486-489, in points
+    const size_t e = v->complex_ ? 2 : 1, p = v->points() / channels;
+    size_t total;
+    if (!mat_extent(channels, p, 0, e, &total)) return BDSP_ERR_UNSUPPORTED;
+    std::unique_ptr<DevMat<T>> m(new DevMat<T>());
+    meta_copy<T>(&m->v, v); // a poisoned source: no points, so `channels` empty rows, and its NaN delta poisons the result
+    m->rows = channels;
+    BDSP_TRY(m->v.reserve(total ? total : 1));
+    BDSP_TRY(tp_transpose<T>(v->data, m->v.data, p, channels, v->complex_, lib_stream()));
+    m->v.valid_len = total;
+    *out = m.release();
+    return (*out)->v.erroneous() ? BDSP_ERR_POISONED : BDSP_OK;
+}
+
+// y[j * rows + r] = m[r][j]: the transpose of the matrix, flat
+template <typename T>
+int mat_to_interleaved(const DevMat<T>* m, DevVec<T>** out)
+{
+    *out = nullptr;
+    const size_t total = m->v.valid_len;
+    std::unique_ptr<DevVec<T>> y(new DevVec<T>());
+    meta_copy<T>(y.get(), &m->v);
+    BDSP_TRY(y->reserve(total ? total : 1));
+    BDSP_TRY(tp_transpose<T>(m->v.data, y->data, m->rows, m->row_points(), m->v.complex_, lib_stream()));
+    y->valid_len = total;
+    *out = y.release();
+    return (*out)->erroneous() ? BDSP_ERR_POISONED : BDSP_OK;
+}
+
+// every point of every row followed by factor - 1 zeros: the rows lie back to back, so the flat allocation IS the
+// per-row result -- op_zero_interleave's one launch over valid_len
+template <typename T>
+int mat_zero_interleave(DevMat<T>* m, int factor)
+{
+    if (factor <= 1) return BDSP_OK; // data_reorganization.rs:256-258
+    size_t nl;
+    if (!mat_extent(m->v.valid_len, (size_t)factor, 0, 1, &nl)) return BDSP_ERR_UNSUPPORTED;
+    BDSP_TRY(m->v.reserve(nl));
+    BDSP_TRY(rg_zero_interleave<T>(m->v.data, m->v.buf, m->v.valid_len, m->v.complex_ ? 2 : 1, (size_t)factor, lib_stream()));
+    m->v.trade();
+    m->v.valid_len = nl;
+    return BDSP_OK;
+}
+
 // convolve_signal with ONE impulse response shared by all rows (matrix/src/time_freq.rs:421-431)
 template <typename T>
 int mat_convolve_signal(DevMat<T>* m, const DevVec<T>* h)
@@ -3323,6 +3390,19 @@ BDSP_MAT_EW(64, double, MatBuf64, VecBuf64)
 BDSP_MAT_FRAME(32, float, MatBuf32, VecBuf32)
 BDSP_MAT_FRAME(64, double, MatBuf64, VecBuf64)
 #undef BDSP_MAT_FRAME
+
+// across the rows: transpose, interleaved channels <-> rows, zero interleave (mat_transpose .. mat_zero_interleave above)
+#define BDSP_MAT_TRANSPOSE(SFX, T, MB, VB)                                                                  \
+    int32_t bdsp_hip_mat_transpose##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_transpose<T>(a)); } \
+    int32_t bdsp_hip_mat_from_interleaved##SFX(const VB* vector, size_t channels, MB** out)                 \
+    { DevMat<T>* m = nullptr; const int c = mat_from_interleaved<T>(H<T>(vector), channels, &m); *out = reinterpret_cast<MB*>(m); return c; } \
+    int32_t bdsp_hip_mat_to_interleaved##SFX(const MB* m, VB** out)                                         \
+    { DevVec<T>* y = nullptr; const int c = mat_to_interleaved<T>(MC##SFX(m), &y); *out = reinterpret_cast<VB*>(y); return c; } \
+    int32_t bdsp_hip_mat_zero_interleave##SFX(MB* m, int32_t factor) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_zero_interleave<T>(a, factor)); }
+
+BDSP_MAT_TRANSPOSE(32, float, MatBuf32, VecBuf32)
+BDSP_MAT_TRANSPOSE(64, double, MatBuf64, VecBuf64)
+#undef BDSP_MAT_TRANSPOSE
 
 // ---------------------------------------------------------------------------------------------- B3
 int bdsp_hip_dev_fft(int elem, void* data, void* scratch, size_t points, size_t batch, unsigned flags,

@@ -135,6 +135,48 @@ class DspMat:
         code = _lib.check(self._fn("overlap_add")(self._h, int(hop), C.byref(out)), "mat_overlap_add" + self._sfx)
         return code, (DspVec(_handle=out.value, _sfx=self._sfx) if out.value else None)
 
+    # ------------------------------------------------------------------ across the rows
+    # One tiled transpose of whole elements (a complex pair stays together) serves all three; one launch each, no host
+    # round trip, no pointer table, no synchronisation.
+    def transpose(self):
+        """Rows become columns in place: rows() <- the old row_points(), row_points() <- the old rows(), element (r, j)
+        moves to (j, r); bit-exact.  After it every row operation (fft, windowed_fft, statistics, convolve, diff, ...)
+        works down the old columns.  Number space, domain and delta stay -- delta belongs to the row axis, so its meaning
+        after a transpose is the caller's.  A matrix without rows or with empty rows becomes a matrix without rows
+        (transposing an empty matrix twice does not bring the row count back).  Codes: 0; -1 for a poisoned matrix, which
+        is left as it is.  Goes through the trade buffer like swap_halves and does not allocate, so it can be captured
+        into a Graph."""
+        return self._call("transpose")
+
+    @classmethod
+    def from_interleaved(cls, vector, channels):
+        """(code, DspMat-or-None): the DspVec `vector` of interleaved channels as a matrix of `channels` rows x
+        points // channels points -- row c, point j is x[j * channels + c] (in points), every row bit-equal to target c of
+        DspVec.split_into with `channels` targets.  Number space, domain and delta are the vector's, which stays as it
+        is.  An empty vector gives `channels` empty rows.  Codes: 0; 7 if channels is 0 or does not divide the points (no
+        matrix); -1 for a poisoned vector (the matrix is poisoned too).  Allocates, so it cannot be captured into a
+        Graph."""
+        out = C.c_void_p()
+        fn = getattr(lib, "bdsp_hip_mat_from_interleaved" + vector._sfx)
+        code = _lib.check(fn(vector._h, int(channels), C.byref(out)), "mat_from_interleaved" + vector._sfx)
+        return code, (cls(_handle=out.value, _sfx=vector._sfx) if out.value else None)
+
+    def to_interleaved(self):
+        """(code, DspVec-or-None): the rows interleaved into one vector of rows() * row_points() points, y[j * rows + r] =
+        row r's point j -- bit-equal to DspVec.merge of the rows, and the inverse of from_interleaved.  Number space,
+        domain and delta are the matrix's, which stays as it is.  Codes: 0 (a matrix without rows gives an empty vector);
+        -1 for a poisoned matrix (the vector is poisoned too).  Allocates, so it cannot be captured into a Graph."""
+        out = C.c_void_p()
+        code = _lib.check(self._fn("to_interleaved")(self._h, C.byref(out)), "mat_to_interleaved" + self._sfx)
+        return code, (DspVec(_handle=out.value, _sfx=self._sfx) if out.value else None)
+
+    def zero_interleave(self, factor):
+        """Every point of every row is followed by factor - 1 zeros, as DspVec.zero_interleave on every row; row_points()
+        grows by `factor`, rows, delta and domain stay.  Codes: 0 (a factor <= 1 leaves the matrix as it is); -1 for a
+        matrix that was poisoned before.  Grows the buffers on the first call at a size, so only a repeated call can be
+        captured into a Graph."""
+        return self._call("zero_interleave", int(factor))
+
     # ------------------------------------------------------------------ elementwise
     def scale(self, factor):
         if isinstance(factor, complex):

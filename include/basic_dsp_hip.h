@@ -925,6 +925,31 @@ int32_t bdsp_hip_mat_set_mag_phase32(MatBuf32 *m, const MatBuf32 *mag, const Mat
 int32_t bdsp_hip_mat_from_frames32(const VecBuf32 *vector, size_t frame_points, size_t hop, int32_t pad_tail, MatBuf32 **out);
 int32_t bdsp_hip_mat_overlap_add32(const MatBuf32 *m, size_t hop, VecBuf32 **out);
 int32_t bdsp_hip_mat_from_vectors32(const VecBuf32 *const *vectors, size_t count, MatBuf32 **out);
+/* Across the rows: one tiled transpose of whole elements (a real scalar or a complex pair stays together) serves
+ * transpose, from_interleaved and to_interleaved -- the reference's split_into and merge
+ * (vector/src/vector_types/general/data_reorganization.rs:477-555) with the rows of ONE matrix as targets and sources,
+ * so no pointer table and no synchronisation; zero_interleave is the same file's zero_interleave on every row.  One launch each, bit-exact.
+ * transpose(m): in place through the trade buffer, rows <- the old row points, row points <- the old rows; nothing is
+ * allocated, so it can be captured into a graph like swap_halves.  Number space, domain and delta stay: delta belongs to
+ * the row axis, the axis across the rows has none, and what delta means after a transpose is the caller's business.  A
+ * matrix without rows or with empty rows becomes a matrix WITHOUT ROWS, 0 -- so transposing an empty matrix twice does
+ * not bring its row count back.  A poisoned matrix: -1, untouched, still poisoned.
+ * from_interleaved(vector, channels): a new matrix of `channels` rows x P / channels points, row c, point j =
+ * x[j * channels + c] (in points), every row bit-equal to target c of split_into with `channels` targets.  Number space,
+ * domain and delta are the vector's, which stays as it is.  channels == 0 or P % channels != 0: 7, *out = NULL.  An
+ * empty vector: `channels` empty rows, 0.
+ * to_interleaved(m): the inverse -- a new vector of rows * row points points, y[j * rows + r] = m[r][j], bit-equal to
+ * merge of the rows; the matrix stays as it is.  A matrix without rows: an empty vector, 0.
+ * Both allocate their result, hand it back through *out (to be deleted by the caller with bdsp_hip_mat_delete /
+ * delete_vector) and cannot be captured into a graph; a poisoned source gives a poisoned result and -1; a failed
+ * allocation or a result too long for the address space returns the backend code (<= -100) with *out = NULL.
+ * zero_interleave(m, factor): every point of every row is followed by factor - 1 zeros, as zero_interleave on every row;
+ * row points grow by `factor`.  factor <= 1: nothing happens, 0.  -1 for a poisoned matrix.  It grows the buffers, so a
+ * captured graph must not contain the first call at a size. */
+int32_t bdsp_hip_mat_transpose32(MatBuf32 *m);
+int32_t bdsp_hip_mat_from_interleaved32(const VecBuf32 *vector, size_t channels, MatBuf32 **out);
+int32_t bdsp_hip_mat_to_interleaved32(const MatBuf32 *m, VecBuf32 **out);
+int32_t bdsp_hip_mat_zero_interleave32(MatBuf32 *m, int32_t factor);
 
 MatBuf64 *bdsp_hip_mat_new64(int32_t is_complex, int32_t domain, size_t rows, size_t row_len, double delta); /* row_len in scalars; zero filled */
 void bdsp_hip_mat_delete64(MatBuf64 *m);
@@ -1086,6 +1111,11 @@ int32_t bdsp_hip_mat_set_mag_phase64(MatBuf64 *m, const MatBuf64 *mag, const Mat
 int32_t bdsp_hip_mat_from_frames64(const VecBuf64 *vector, size_t frame_points, size_t hop, int32_t pad_tail, MatBuf64 **out);
 int32_t bdsp_hip_mat_overlap_add64(const MatBuf64 *m, size_t hop, VecBuf64 **out);
 int32_t bdsp_hip_mat_from_vectors64(const VecBuf64 *const *vectors, size_t count, MatBuf64 **out);
+/* across the rows (data_reorganization.rs:477-555): see bdsp_hip_mat_transpose32 */
+int32_t bdsp_hip_mat_transpose64(MatBuf64 *m);
+int32_t bdsp_hip_mat_from_interleaved64(const VecBuf64 *vector, size_t channels, MatBuf64 **out);
+int32_t bdsp_hip_mat_to_interleaved64(const MatBuf64 *m, VecBuf64 **out);
+int32_t bdsp_hip_mat_zero_interleave64(MatBuf64 *m, int32_t factor);
 
 /* ==========================================================================================
  * B3 -- kernels on caller-owned DEVICE memory.  `stream` is a hipStream_t passed as void*
