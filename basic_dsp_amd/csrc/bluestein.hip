@@ -243,36 +243,48 @@ template <typename T> int bs_kernel(const T* c, T* b, size_t n, size_t m, hipStr
     BDSP_LAUNCH_CHECK();
     return BDSP_OK;
 }
+// grid.y carries the rows and stops at 65535: more rows go in pieces of that many (rows lie back to back in every buffer)
+constexpr size_t BS_MAX_GRID_Y = 65535;
+
 template <typename T>
 int bs_pre(const T* x, T* a, const T* c, size_t n, size_t m, size_t batch, bool in_real, T in_scale, size_t rot,
            int window_id, T alpha, hipStream_t s)
 {
-    dim3 grid(bs_grid(m), (unsigned)batch);
-    if (in_real)
-        hipLaunchKernelGGL((k_bs_pre<T, true>), grid, dim3(256), 0, s, x, reinterpret_cast<cpx<T>*>(a),
-                           reinterpret_cast<const cpx<T>*>(c), (unsigned long long)n, (unsigned long long)m, in_scale,
-                           (unsigned long long)rot, window_id, alpha);
-    else
-        hipLaunchKernelGGL((k_bs_pre<T, false>), grid, dim3(256), 0, s, x, reinterpret_cast<cpx<T>*>(a),
-                           reinterpret_cast<const cpx<T>*>(c), (unsigned long long)n, (unsigned long long)m, in_scale,
-                           (unsigned long long)rot, window_id, alpha);
-    BDSP_LAUNCH_CHECK();
+    for (size_t r0 = 0; r0 < batch; r0 += BS_MAX_GRID_Y) {
+        const size_t rows = batch - r0 < BS_MAX_GRID_Y ? batch - r0 : BS_MAX_GRID_Y;
+        dim3 grid(bs_grid(m), (unsigned)rows);
+        const T* xp = x + r0 * n * (in_real ? 1 : 2);
+        cpx<T>* ap = reinterpret_cast<cpx<T>*>(a) + r0 * m;
+        if (in_real)
+            hipLaunchKernelGGL((k_bs_pre<T, true>), grid, dim3(256), 0, s, xp, ap, reinterpret_cast<const cpx<T>*>(c),
+                               (unsigned long long)n, (unsigned long long)m, in_scale, (unsigned long long)rot, window_id,
+                               alpha);
+        else
+            hipLaunchKernelGGL((k_bs_pre<T, false>), grid, dim3(256), 0, s, xp, ap, reinterpret_cast<const cpx<T>*>(c),
+                               (unsigned long long)n, (unsigned long long)m, in_scale, (unsigned long long)rot, window_id,
+                               alpha);
+        BDSP_LAUNCH_CHECK();
+    }
     return BDSP_OK;
 }
 template <typename T>
 int bs_post(const T* conv, T* out, const T* c, size_t n, size_t m, size_t batch, int out_kind, size_t rot,
             int div_window_id, T alpha, hipStream_t s)
 {
-    dim3 grid(bs_grid(n), (unsigned)batch);
+    for (size_t r0 = 0; r0 < batch; r0 += BS_MAX_GRID_Y) {
+        const size_t rows = batch - r0 < BS_MAX_GRID_Y ? batch - r0 : BS_MAX_GRID_Y;
+        dim3 grid(bs_grid(n), (unsigned)rows);
+        const cpx<T>* cp = reinterpret_cast<const cpx<T>*>(conv) + r0 * m;
+        T* op = out + r0 * n * (out_kind == 0 ? 2 : 1);
 #define BDSP_POST(K)                                                                                          \
-    hipLaunchKernelGGL((k_bs_post<T, K>), grid, dim3(256), 0, s, reinterpret_cast<const cpx<T>*>(conv), out,  \
-                       reinterpret_cast<const cpx<T>*>(c), (unsigned long long)n, (unsigned long long)m,     \
-                       (unsigned long long)rot, div_window_id, alpha)
-    if (out_kind == 0) BDSP_POST(0);
-    else if (out_kind == 1) BDSP_POST(1);
-    else BDSP_POST(2);
+    hipLaunchKernelGGL((k_bs_post<T, K>), grid, dim3(256), 0, s, cp, op, reinterpret_cast<const cpx<T>*>(c),  \
+                       (unsigned long long)n, (unsigned long long)m, (unsigned long long)rot, div_window_id, alpha)
+        if (out_kind == 0) BDSP_POST(0);
+        else if (out_kind == 1) BDSP_POST(1);
+        else BDSP_POST(2);
 #undef BDSP_POST
-    BDSP_LAUNCH_CHECK();
+        BDSP_LAUNCH_CHECK();
+    }
     return BDSP_OK;
 }
 
