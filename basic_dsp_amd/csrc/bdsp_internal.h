@@ -161,7 +161,6 @@ template <typename T> int ew_real_offset(T* x, size_t len, bool is_complex, T f,
 template <typename T> int ew_complex_scale(T* x, size_t len, T re, T im, hipStream_t s);
 template <typename T> int ew_complex_offset(T* x, size_t len, T re, T im, hipStream_t s);
 template <typename T> int ew_binary(T* x, const T* y, size_t len, bool is_complex, int op, hipStream_t s);
-template <typename T> int ew_binary_smaller(T* x, const T* y, size_t len, size_t ylen, bool is_complex, int op, hipStream_t s);
 template <typename T> int ew_point_table(T* x, size_t len, bool is_complex, const T* table, bool divide, hipStream_t s);
 template <typename T> int ew_conj(T* x, size_t len, hipStream_t s);
 template <typename T> int ew_mul_cexp(T* x, size_t len, T a, T b, hipStream_t s);
@@ -178,12 +177,8 @@ template <typename T> int ew_linear_phase(T* x, size_t len, T delay, hipStream_t
 template <typename T> int ew_spectrum_resample(const T* in, T* out, size_t src_points, size_t dst_points, int mode, int fid, T rolloff, T ratio, double phase_inc, hipStream_t s);
 
 // reorg.hip
-template <typename T> int rg_rotate(const T* in, T* out, size_t points, size_t elem, size_t shift, hipStream_t s);
 template <typename T> int rg_wrap_copy(const T* in, T* out, size_t points, size_t elem, size_t total, long long start, hipStream_t s);
-template <typename T> int rg_reverse(const T* in, T* out, size_t points, size_t elem, hipStream_t s);
-template <typename T> int rg_zero_pad(const T* in, T* out, size_t len_before, bool is_complex, size_t points, int option, hipStream_t s);
 template <typename T> int rg_zero_interleave(const T* in, T* out, size_t len, size_t elem, size_t factor, hipStream_t s);
-template <typename T> int rg_mirror(const T* in, T* out, size_t len, hipStream_t s);
 template <typename T> int rg_decimate(const T* in, T* out, size_t out_points, size_t elem, size_t factor, size_t delay, hipStream_t s);
 
 // interp.hip
@@ -214,9 +209,6 @@ enum MathFn {
 };
 template <typename T> int ew_math(T* x, size_t len, bool is_complex, int fn, T arg, hipStream_t s);
 template <typename T> int vm_diff(const T* in, T* out, size_t n_out, size_t step, bool with_start, hipStream_t s);
-template <typename T> size_t vm_cum_sum_scratch(size_t len, bool is_complex);
-template <typename T> int vm_cum_sum(T* x, size_t len, bool is_complex, void* scratch, hipStream_t s);
-template <typename T> int vm_unwrap(T* x, size_t len, T divisor, hipStream_t s);
 template <typename T> int vm_complex_split(const T* x, T* a, T* b, size_t points, int kind, hipStream_t s);
 template <typename T> int vm_complex_join(T* x, const T* a, const T* b, size_t points, int kind, hipStream_t s);
 template <typename T> int vm_split_merge(T* whole, T* const* parts_dev, size_t len, bool is_complex, size_t n, bool merge, hipStream_t s);
@@ -264,7 +256,7 @@ bool mc_fused_len(size_t l); // a power of two in [16, 4096]: mc_correlate_fused
 template <typename T>
 int mc_correlate_fused(const T* in, T* out, const T* arg, size_t arg_stride, size_t rows, size_t p, size_t l, hipStream_t s);
 
-// mat_scan.hip -- diff, cum_sum and unwrap of every row of a matrix; the launch counts do not depend on `rows`
+// mat_scan.hip -- diff, cum_sum and unwrap of every row of a matrix (a vector is one row); the launch counts do not depend on `rows`
 // `rows` rows of row_len scalars -> rows of row_len - step (diff) or row_len (with_start) scalars, dense, out of place
 template <typename T> int ms_diff(const T* in, T* out, size_t rows, size_t row_len, size_t step, bool with_start, hipStream_t s);
 // in-place prefix sums per row; `scratch`: ms_cum_sum_scratch bytes (0 for rows of at most one scan chunk)
@@ -316,13 +308,13 @@ int mt_conv_direct(const T* in, T* out, size_t rows, size_t points, bool is_comp
 template <typename T>
 int mt_interpolate_real(const T* in, T* out, size_t rows, size_t len, T factor, T delay, bool hermite, hipStream_t s);
 
-// mat_ew.hip -- the row-aware elementwise operations of a matrix; one launch each, whatever `rows`
+// mat_ew.hip -- the row-aware elementwise operations of a matrix (a vector is one row); one launch each, whatever `rows`
 // z[r][k] *= exp(j (a k + b)) for `rows` rows of `points` complex points, k from 0 in every row; in place
 template <typename T> int mw_cexp(T* x, size_t rows, size_t points, double a, double b, hipStream_t s);
 // out[r][i] = in[r][points - 1 - i] in elements (complex pairs if is_complex); out of place
 template <typename T> int mw_reverse(const T* in, T* out, size_t rows, size_t points, bool is_complex, hipStream_t s);
-// x[r][i] (.)= y[r * ystride + i mod ypoints] in elements, op 0 .. 3 = add, sub, mul, div (ew_binary_smaller's
-// expressions); ystride 0: one operand for every row; ypoints must divide points (else BDSP_ERR_ARG_LENGTH); in place
+// x[r][i] (.)= y[r * ystride + i mod ypoints] in elements, op 0 .. 3 = add, sub, mul, div (elementary.rs:591-640);
+// ystride 0: one operand for every row; ypoints must divide points (else BDSP_ERR_ARG_LENGTH); in place
 template <typename T>
 int mw_smaller(T* x, const T* y, size_t rows, size_t points, size_t ypoints, size_t ystride, bool is_complex, int op,
                hipStream_t s);
@@ -339,11 +331,11 @@ int mf_overlap_add(const T* m, T* y, size_t rows, size_t frame_points, size_t ho
 // out[r] = vectors[r] (a DEVICE table of `rows` device pointers to `points` elements each)
 template <typename T>
 int mf_from_vectors(const T* const* vectors, T* out, size_t rows, size_t points, bool is_complex, hipStream_t s);
-// every row as rg_zero_pad (option 0 End, 1 Surround, else Center); BDSP_ERR_ARG_LENGTH unless points > points_before
+// every row zero-padded (option 0 End, 1 Surround, else Center: mat_frame_core.h); BDSP_ERR_ARG_LENGTH unless points > points_before
 template <typename T>
 int mf_zero_pad(const T* in, T* out, size_t rows, size_t points_before, size_t points, bool is_complex, int option,
                 hipStream_t s);
-// every row as rg_rotate: out[r][i] = in[r][(i + shift) mod points]
+// every row rotated: out[r][i] = in[r][(i + shift) mod points]
 template <typename T>
 int mf_rotate(const T* in, T* out, size_t rows, size_t points, size_t shift, bool is_complex, hipStream_t s);
 

@@ -917,13 +917,14 @@ int op_interpolatef(DevVec<T>* v, int fid, T rolloff, T factor, T delay, size_t 
     return BDSP_OK;
 }
 
+// `rows` equally long rows back to back (a vector is one row; the matrix entries pass theirs), as op_fft: one launch
 template <typename T>
-int op_swap(DevVec<T>* v, bool forward)
+int op_swap(DevVec<T>* v, bool forward, size_t rows = 1)
 {
-    size_t p = v->points();
+    const size_t p = rows ? v->points() / rows : 0;
     if (p == 0) return BDSP_OK;
-    size_t shift = forward ? p - p / 2 : p / 2;
-    BDSP_TRY(rg_rotate<T>(v->data, v->buf, p, v->complex_ ? 2 : 1, shift, lib_stream()));
+    const size_t shift = forward ? p - p / 2 : p / 2;
+    BDSP_TRY(mf_rotate<T>(v->data, v->buf, rows, p, shift, v->complex_, lib_stream()));
     v->trade();
     return BDSP_OK;
 }
@@ -935,7 +936,7 @@ int op_zero_pad(DevVec<T>* v, size_t points, int option)
     if (len <= v->valid_len) return BDSP_ERR_ARG_LENGTH; // data_reorganization.rs:415-417
     BDSP_TRY(v->reserve(len));
     int opt = option == 0 ? 0 : (option == 1 ? 1 : 2); // interop/src/lib.rs:194-200
-    BDSP_TRY(rg_zero_pad<T>(v->data, v->buf, v->valid_len, v->complex_, points, opt, lib_stream()));
+    BDSP_TRY(mf_zero_pad<T>(v->data, v->buf, 1, v->valid_len / step, points, v->complex_, opt, lib_stream()));
     v->trade();
     v->valid_len = len;
     return BDSP_OK;
@@ -973,7 +974,7 @@ int op_mirror(DevVec<T>* v)
     if (v->valid_len < 2) return BDSP_OK;
     size_t nl = 2 * v->valid_len - 2;
     BDSP_TRY(v->reserve(nl));
-    BDSP_TRY(rg_mirror<T>(v->data, v->buf, v->valid_len, lib_stream()));
+    BDSP_TRY(sy_mirror_rows<T>(v->data, v->buf, 1, v->valid_len / 2, 0, false, (T)1, nullptr, lib_stream()));
     v->trade();
     v->valid_len = nl;
     return BDSP_OK;
@@ -1304,7 +1305,8 @@ int op_binary_smaller(DevVec<T>* v, const DevVec<T>* o, int op)
 {
     if (o->valid_len == 0 || v->valid_len % o->valid_len != 0) return BDSP_ERR_ARG_LENGTH; // elementary.rs:613-617
     if (!meta_agrees(v, o)) return BDSP_ERR_META_DATA;
-    return ew_binary_smaller<T>(v->data, o->data, v->valid_len, o->valid_len, v->complex_, op, lib_stream());
+    const size_t e = v->complex_ ? 2 : 1;
+    return mw_smaller<T>(v->data, o->data, 1, v->valid_len / e, o->valid_len / e, 0, v->complex_, op, lib_stream());
 }
 
 // Host-sampled callbacks (interop/src/lib.rs:245-377).  A window callback is sampled for every point
@@ -1478,21 +1480,36 @@ int op_diff(DevVec<T>* v, bool with_start)
     return BDSP_OK;
 }
 
+// cum_sum and unwrap of `rows` equally long rows back to back (a vector is one row; the matrix entries pass theirs), as
+// op_fft: the launch counts do not depend on `rows` (mat_scan.hip)
 template <typename T>
-int op_cum_sum(DevVec<T>* v)
+int op_cum_sum(DevVec<T>* v, size_t rows = 1)
 {
-    if (v->valid_len == 0) return BDSP_OK;
+    const size_t p = rows ? v->points() / rows : 0;
+    if (p == 0) return BDSP_OK;
     hipStream_t s = lib_stream();
     WsBlock sc;
-    BDSP_TRY(sc.alloc(vm_cum_sum_scratch<T>(v->valid_len, v->complex_), s));
-    return vm_cum_sum<T>(v->data, v->valid_len, v->complex_, sc.p, s);
+    const size_t bytes = ms_cum_sum_scratch<T>(rows, p, v->complex_);
+    if (bytes) BDSP_TRY(sc.alloc(bytes, s));
+    return ms_cum_sum<T>(v->data, rows, p, v->complex_, sc.p, s);
 }
 
 template <typename T>
-int op_unwrap(DevVec<T>* v, T divisor)
+int op_unwrap(DevVec<T>* v, T divisor, size_t rows = 1)
 {
-    if (v->complex_) { v->poison(); return BDSP_OK; }
-    return vm_unwrap<T>(v->data, v->valid_len, divisor, lib_stream());
+    if (v->complex_) { v->poison(); return BDSP_OK; } // assert_real!, real_ops.rs:222-233
+    return ms_unwrap<T>(v->data, rows, rows ? v->valid_len / rows : 0, divisor, lib_stream());
+}
+
+// reverse, row-aware in the same way (mat_ew.hip)
+template <typename T>
+int op_reverse(DevVec<T>* v, size_t rows = 1)
+{
+    const size_t p = rows ? v->points() / rows : 0;
+    if (p == 0) return BDSP_OK;
+    BDSP_TRY(mw_reverse<T>(v->data, v->buf, rows, p, v->complex_, lib_stream()));
+    v->trade();
+    return BDSP_OK;
 }
 
 // get_real_imag / get_mag_phase (complex_to_real.rs:674-712): both targets are resized to `points` reals; a real
@@ -1802,7 +1819,8 @@ int mat_binary_vector(DevMat<T>* m, const DevVec<T>* o, int op)
     // every row (.)= the same vector: the wrap-around kernel with period = one row
     if (o->valid_len != m->row_len()) return BDSP_ERR_SAME_SIZE;
     if (!meta_agrees(&m->v, o)) return BDSP_ERR_META_DATA;
-    return ew_binary_smaller<T>(m->v.data, o->data, m->v.valid_len, o->valid_len, m->v.complex_, op, lib_stream());
+    const size_t p = m->row_points();
+    return mw_smaller<T>(m->v.data, o->data, m->rows, p, p, 0, m->v.complex_, op, lib_stream());
 }
 
 template <typename T>
@@ -1819,25 +1837,13 @@ int mat_window(DevMat<T>* m, int window, bool unapply)
 }
 
 template <typename T>
-int mat_swap(DevMat<T>* m, bool forward)
-{
-    const size_t p = m->row_points();
-    if (p == 0) return BDSP_OK;
-    const size_t shift = forward ? p - p / 2 : p / 2;
-    // one launch over rows x points: every row as rg_rotate on it
-    BDSP_TRY(mf_rotate<T>(m->v.data, m->v.buf, m->rows, p, shift, m->v.complex_, lib_stream()));
-    m->v.trade();
-    return BDSP_OK;
-}
-
-template <typename T>
 int mat_zero_pad(DevMat<T>* m, size_t points, int option)
 {
     const size_t step = m->v.complex_ ? 2 : 1, len = points * step, rl = m->row_len();
     if (len <= rl) return BDSP_ERR_ARG_LENGTH; // an argument error comes first, as in every other call
     if (m->v.erroneous()) return BDSP_OK; // a poisoned matrix stays poisoned: padding its empty rows would hide the error
     const int opt = option == 0 ? 0 : (option == 1 ? 1 : 2);
-    // one launch over rows x points: every row as rg_zero_pad on it
+    // one launch over rows x points
     BDSP_TRY(m->v.reserve(m->rows * len));
     BDSP_TRY(mf_zero_pad<T>(m->v.data, m->v.buf, m->rows, rl / step, points, m->v.complex_, opt, lib_stream()));
     m->v.trade();
@@ -1942,7 +1948,7 @@ int mat_from_vectors(const DevVec<T>* const* vectors, size_t count, DevMat<T>** 
 // Across the rows (mat_transpose.hip): one tiled transpose of whole elements serves transpose, from_interleaved and
 // to_interleaved (the reference's split_into and merge, data_reorganization.rs:477-555, with the rows of one matrix as
 // targets and sources); one launch each, no pointer table, no synchronisation.
-// In place through the trade buffer, as mat_swap: rows <- the old row points, the scalar count stays, so nothing is
+// In place through the trade buffer, as op_swap: rows <- the old row points, the scalar count stays, so nothing is
 // allocated.  An empty matrix loses its rows; a poisoned one is left alone (mat_code answers -1).
 template <typename T>
 int mat_transpose(DevMat<T>* m)
@@ -2074,9 +2080,8 @@ int mat_multiply_frequency_response(DevMat<T>* m, int fid, T rolloff, T ratio)
     return ew_freq_response_rows<T>(m->v.data, m->rows, m->row_len(), m->v.complex_, fid, rolloff, ratio, false, lib_stream());
 }
 
-// diff / diff_with_start / cum_sum / wrap / unwrap of every row (mat_scan.hip): each row as the vector function of the
-// same name (op_diff, op_cum_sum, op_math(MATH_WRAP), op_unwrap above).  diff shortens every row by one point; rows
-// that are empty stay empty.
+// diff / diff_with_start of every row (mat_scan.hip): each row as op_diff on it.  diff shortens every row by one point;
+// rows that are empty stay empty.  (cum_sum and unwrap: op_cum_sum and op_unwrap with the matrix's rows.)
 template <typename T>
 int mat_diff(DevMat<T>* m, bool with_start)
 {
@@ -2087,25 +2092,6 @@ int mat_diff(DevMat<T>* m, bool with_start)
     m->v.trade();
     m->v.valid_len = m->rows * n_out;
     return BDSP_OK;
-}
-
-template <typename T>
-int mat_cum_sum(DevMat<T>* m)
-{
-    const size_t p = m->row_points();
-    if (m->rows == 0 || p == 0) return BDSP_OK;
-    hipStream_t s = lib_stream();
-    WsBlock sc;
-    const size_t bytes = ms_cum_sum_scratch<T>(m->rows, p, m->v.complex_);
-    if (bytes) BDSP_TRY(sc.alloc(bytes, s));
-    return ms_cum_sum<T>(m->v.data, m->rows, p, m->v.complex_, sc.p, s);
-}
-
-template <typename T>
-int mat_unwrap(DevMat<T>* m, T divisor)
-{
-    if (m->v.complex_) { m->v.poison(); return BDSP_OK; } // assert_real!, real_ops.rs:222-233
-    return ms_unwrap<T>(m->v.data, m->rows, m->row_len(), divisor, lib_stream());
 }
 
 template <typename T>
@@ -2261,7 +2247,7 @@ int mat_correlate(DevMat<T>* m, const DevVec<T>* o, size_t o_rows, size_t l, siz
     BDSP_TRY(fft_two_buffers<T>(m->v.data, m->v.buf, l, rows, false, 0, (T)1, -1, (T)0, &in_b, s));
     if (in_b) m->v.trade();
     if (arg_stride) BDSP_TRY(ew_binary<T>(m->v.data, o->data, m->v.valid_len, true, 2, s));
-    else BDSP_TRY(ew_binary_smaller<T>(m->v.data, o->data, m->v.valid_len, 2 * l, true, 2, s));
+    else BDSP_TRY(mw_smaller<T>(m->v.data, o->data, rows, l, l, 0, true, 2, s));
     // plain_ifft -> scale(1/l) -> swap_halves ride on the inverse transform, as in op_correlate
     BDSP_TRY(fft_two_buffers<T>(m->v.data, m->v.buf, l, rows, true, BDSP_FFT_SHIFT_OUT, (T)1 / (T)l, -1, (T)0, &in_b, s));
     if (in_b) m->v.trade();
@@ -2541,16 +2527,6 @@ int mat_mirror(DevMat<T>* m)
 // flat ew_complex_to_real / vm_complex_split / vm_complex_join over rows * points; reverse, the mixer and *_smaller
 // know the rows.  One launch each, whatever the row count.
 template <typename T>
-int mat_reverse(DevMat<T>* m)
-{
-    const size_t p = m->row_points();
-    if (m->rows == 0 || p == 0) return BDSP_OK;
-    BDSP_TRY(mw_reverse<T>(m->v.data, m->v.buf, m->rows, p, m->v.complex_, lib_stream()));
-    m->v.trade();
-    return BDSP_OK;
-}
-
-template <typename T>
 int mat_mul_cexp(DevMat<T>* m, T a, T b)
 {
     if (!m->v.complex_) { m->v.poison(); return BDSP_OK; } // assert_complex!, complex_ops.rs:81-83
@@ -2757,13 +2733,7 @@ size_t bdsp_hip_overlap_discard_f64(double* x_time, size_t x_len, double* tmp, s
     RES to_imag##SFX(VB* vector) { DevVec<T>* v = H<T>(vector); return finish<T>(v, op_complex_to_real<T>(v, 3)); } \
     RES phase##SFX(VB* vector) { DevVec<T>* v = H<T>(vector); return finish<T>(v, op_complex_to_real<T>(v, 4)); } \
     RES to_complex##SFX(VB* vector) { DevVec<T>* v = H<T>(vector); return finish<T>(v, op_to_complex<T>(v)); } \
-    RES reverse##SFX(VB* vector)                                                                            \
-    {                                                                                                       \
-        DevVec<T>* v = H<T>(vector);                                                                        \
-        int c = rg_reverse<T>(v->data, v->buf, v->points(), v->complex_ ? 2 : 1, lib_stream());             \
-        if (c == BDSP_OK && v->points()) v->trade();                                                        \
-        return finish<T>(v, c);                                                                             \
-    }                                                                                                       \
+    RES reverse##SFX(VB* vector) { DevVec<T>* v = H<T>(vector); return finish<T>(v, op_reverse<T>(v)); }   \
     RES swap_halves##SFX(VB* vector) { DevVec<T>* v = H<T>(vector); return finish<T>(v, op_swap<T>(v, true)); } \
     RES fft_shift##SFX(VB* vector) { DevVec<T>* v = H<T>(vector); return finish<T>(v, op_swap<T>(v, true)); } \
     RES ifft_shift##SFX(VB* vector) { DevVec<T>* v = H<T>(vector); return finish<T>(v, op_swap<T>(v, false)); } \
@@ -3169,9 +3139,9 @@ BDSP_STATS(64, double, VecBuf64)
     int32_t bdsp_hip_mat_windowed_ifft##SFX(MB* m, int32_t window) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_fft<T>(&a->v, true, true, window < 0 ? 3 : window, a->rows)); } \
     int32_t bdsp_hip_mat_apply_window##SFX(MB* m, int32_t window) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_window<T>(a, window, false)); } \
     int32_t bdsp_hip_mat_unapply_window##SFX(MB* m, int32_t window) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_window<T>(a, window, true)); } \
-    int32_t bdsp_hip_mat_swap_halves##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_swap<T>(a, true)); } \
-    int32_t bdsp_hip_mat_fft_shift##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_swap<T>(a, true)); } \
-    int32_t bdsp_hip_mat_ifft_shift##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_swap<T>(a, false)); } \
+    int32_t bdsp_hip_mat_swap_halves##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_swap<T>(&a->v, true, a->rows)); } \
+    int32_t bdsp_hip_mat_fft_shift##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_swap<T>(&a->v, true, a->rows)); } \
+    int32_t bdsp_hip_mat_ifft_shift##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_swap<T>(&a->v, false, a->rows)); } \
     int32_t bdsp_hip_mat_zero_pad##SFX(MB* m, size_t points, int32_t option) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_zero_pad<T>(a, points, option)); } \
     int32_t bdsp_hip_mat_convolve_signal##SFX(MB* m, const VB* impulse_response) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_convolve_signal<T>(a, H<T>(impulse_response))); } \
     int32_t bdsp_hip_mat_convolve_signal_mat##SFX(MB* m, const VB* const* impulse_responses, size_t count)  \
@@ -3253,13 +3223,13 @@ BDSP_MAT_CORR(32, float, MatBuf32, VecBuf32)
 BDSP_MAT_CORR(64, double, MatBuf64, VecBuf64)
 #undef BDSP_MAT_CORR
 
-// differences, running sums, phase wrapping of the rows (mat_diff / mat_cum_sum / mat_unwrap above)
+// differences, running sums, phase wrapping of the rows (mat_diff, and op_cum_sum / op_unwrap above with the matrix's rows)
 #define BDSP_MAT_SCAN(SFX, T, MB)                                                                           \
     int32_t bdsp_hip_mat_diff##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_diff<T>(a, false)); } \
     int32_t bdsp_hip_mat_diff_with_start##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_diff<T>(a, true)); } \
-    int32_t bdsp_hip_mat_cum_sum##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_cum_sum<T>(a)); } \
+    int32_t bdsp_hip_mat_cum_sum##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_cum_sum<T>(&a->v, a->rows)); } \
     int32_t bdsp_hip_mat_wrap##SFX(MB* m, T divisor) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_math<T>(&a->v, MATH_WRAP, divisor, true)); } \
-    int32_t bdsp_hip_mat_unwrap##SFX(MB* m, T divisor) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_unwrap<T>(a, divisor)); }
+    int32_t bdsp_hip_mat_unwrap##SFX(MB* m, T divisor) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_unwrap<T>(&a->v, divisor, a->rows)); }
 
 BDSP_MAT_SCAN(32, float, MatBuf32)
 BDSP_MAT_SCAN(64, double, MatBuf64)
@@ -3317,7 +3287,7 @@ BDSP_MAT_INTERP(32, float, MatBuf32)
 BDSP_MAT_INTERP(64, double, MatBuf64)
 #undef BDSP_MAT_INTERP
 
-// math family, reverse, mixer, *_smaller and part operations of the rows (op_math and mat_reverse .. mat_set_pair above)
+// math family, reverse, mixer, *_smaller and part operations of the rows (op_math, op_reverse and mat_mul_cexp .. mat_set_pair above)
 #define BDSP_MAT_EW_M0(SFX, T, MB, NAME, FN, REAL_ONLY)                                                     \
     int32_t bdsp_hip_mat_##NAME##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_math<T>(&a->v, FN, (T)0, REAL_ONLY)); }
 #define BDSP_MAT_EW_M1(SFX, T, MB, NAME, FN, REAL_ONLY)                                                     \
@@ -3351,7 +3321,7 @@ BDSP_MAT_INTERP(64, double, MatBuf64)
     BDSP_MAT_EW_M1(SFX, T, MB, expf_approx, MATH_EXPF_APPROX, true)                                         \
     BDSP_MAT_EW_M1(SFX, T, MB, powf_approx, MATH_POWF_APPROX, true)                                         \
     int32_t bdsp_hip_mat_root##SFX(MB* m, T value) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_math<T>(&a->v, MATH_POWF, (T)1 / value, false)); } /* powf(1 / degree), as root32 */ \
-    int32_t bdsp_hip_mat_reverse##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_reverse<T>(a)); } \
+    int32_t bdsp_hip_mat_reverse##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_reverse<T>(&a->v, a->rows)); } \
     int32_t bdsp_hip_mat_multiply_complex_exponential##SFX(MB* m, T a, T b) { DevMat<T>* x = M##SFX(m); return mat_code<T>(x, mat_mul_cexp<T>(x, a, b)); } \
     int32_t bdsp_hip_mat_add_smaller##SFX(MB* m, const MB* o) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_smaller<T>(a, MC##SFX(o), 0)); } \
     int32_t bdsp_hip_mat_sub_smaller##SFX(MB* m, const MB* o) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_smaller<T>(a, MC##SFX(o), 1)); } \

@@ -337,32 +337,6 @@ template <typename T> int ew_binary(T* x, const T* y, size_t len, bool is_comple
     return BDSP_OK;
 }
 
-// ---- x[i] (.)= y[i mod ylen]: add_smaller / sub_smaller / mul_smaller / div_smaller (elementary.rs:591-640)
-template <typename T, bool CPLX>
-__global__ __launch_bounds__(256) void k_binary_smaller(T* __restrict__ x, const T* __restrict__ y, size_t points,
-                                                         size_t ypoints, int op)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < points; i += (size_t)gridDim.x * blockDim.x) {
-        size_t j = i % ypoints;
-        if (CPLX) { // the four expressions are in mat_ew_core.h, shared with the matrix unit
-            T re, im;
-            smaller_complex<T>(x[2 * i], x[2 * i + 1], y[2 * j], y[2 * j + 1], op, &re, &im);
-            x[2 * i] = re; x[2 * i + 1] = im;
-        } else {
-            x[i] = smaller_real<T>(x[i], y[j], op);
-        }
-    }
-}
-template <typename T> int ew_binary_smaller(T* x, const T* y, size_t len, size_t ylen, bool is_complex, int op, hipStream_t s)
-{
-    const size_t e = is_complex ? 2 : 1, points = len / e, yp = ylen / e;
-    if (points == 0 || yp == 0) return BDSP_OK;
-    if (is_complex) hipLaunchKernelGGL((k_binary_smaller<T, true>), dim3(ew_grid(points)), dim3(256), 0, s, x, y, points, yp, op);
-    else hipLaunchKernelGGL((k_binary_smaller<T, false>), dim3(ew_grid(points)), dim3(256), 0, s, x, y, points, yp, op);
-    BDSP_LAUNCH_CHECK();
-    return BDSP_OK;
-}
-
 // ---- x[point i] *= (or /=) table[i]: host-sampled callback windows / frequency responses ------------
 // (interop/src/lib.rs:245-377: the C callbacks cannot run on the device, so the host samples them once)
 template <typename T, bool CPLX>
@@ -447,7 +421,6 @@ template <typename T> int ew_complex_to_real(const T* x, T* out, size_t len, int
     template int ew_complex_scale<T>(T*, size_t, T, T, hipStream_t);                               \
     template int ew_complex_offset<T>(T*, size_t, T, T, hipStream_t);                              \
     template int ew_binary<T>(T*, const T*, size_t, bool, int, hipStream_t);                       \
-    template int ew_binary_smaller<T>(T*, const T*, size_t, size_t, bool, int, hipStream_t);          \
     template int ew_point_table<T>(T*, size_t, bool, const T*, bool, hipStream_t);                   \
     template int ew_conj<T>(T*, size_t, hipStream_t);                                              \
     template int ew_mul_cexp<T>(T*, size_t, T, T, hipStream_t);                                    \

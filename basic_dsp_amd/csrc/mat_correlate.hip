@@ -128,7 +128,7 @@ int mc_pad_rows(const T* in, T* out, size_t rows, size_t p, size_t l, bool is_co
 {
     if (rows == 0 || l == 0) return BDSP_OK;
     if (l < p) return BDSP_ERR_ARG_LENGTH;
-    const size_t d0 = (l - p) - (l - p) / 2; // rg_zero_pad, option Surround
+    const size_t d0 = (l - p) - (l - p) / 2; // zero_pad, option Surround (mat_frame_core.h, mf_pad_geom)
     const size_t total = rows * l, want = (total + 255) / 256, cap = (size_t)num_cus() * 32;
     const unsigned grid = (unsigned)(want < cap ? want : cap);
     if (is_complex)

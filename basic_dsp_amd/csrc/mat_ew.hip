@@ -1,6 +1,7 @@
 // mat_ew.hip -- the row-aware elementwise operations of a matrix: multiply_complex_exponential, reverse and the
 // wrap-around binary operations add_smaller / sub_smaller / mul_smaller / div_smaller with a matrix or one vector as
-// operand (DspMat methods of the same names).
+// operand (DspMat methods of the same names).  A vector is a matrix of one row: DspVec's reverse and *_smaller
+// launch these kernels too (its mixer keeps elementwise.hip's packet map, which measured faster for one long row).
 //
 // Replaces the row loop of the reference's matrix crate (matrix/src/complex.rs:203-211, general/elementary.rs:117-198
 // forward the traits to the rows one after the other); each row computes what complex_ops.rs:81-105,
@@ -16,9 +17,9 @@
 //   k_mw_smaller  x[r][i] (.)= y[r * ystride + i mod ypoints] (ystride 0: one vector for every row), lanes along the
 //                 flat matrix.
 // The last two divide once per lane and carry the position, the row and the period position from one grid stride to
-// the next.  The per-element arithmetic is elementwise.hip's (mat_ew_core.h), so a row is bit-equal to the vector call
-// on it; the maps are in mat_ew_core.h too, tests/host_sim/sim_mat_ew.cpp runs them with threads as loops.  Built
-// without FMA contraction, as elementwise.hip.
+// the next.  The per-element arithmetic and the maps are in mat_ew_core.h (the mixer's expressions are shared with
+// elementwise.hip, so a row is bit-equal to the vector call on it), tests/host_sim/sim_mat_ew.cpp runs the maps with
+// threads as loops.  Built without FMA contraction, as elementwise.hip.
 #include "bdsp_internal.h"
 #include "mat_ew_core.h"
 
@@ -32,7 +33,7 @@ static inline unsigned mw_grid(size_t blocks)
 }
 
 template <typename T> struct mw_vec2 { typedef T type __attribute__((ext_vector_type(2))); };
-// a whole element (a real scalar or an interleaved complex pair) as one packet, as reorg.hip's packet_of
+// a whole element (a real scalar or an interleaved complex pair) as one packet
 template <typename T, int ELEM> struct mw_packet_of { using type = T; };
 template <typename T> struct mw_packet_of<T, 2> { using type = typename mw_vec2<T>::type; };
 

@@ -1,8 +1,8 @@
-// mat_ew_core.h -- what the matrix unit mat_ew.hip shares with the vector unit elementwise.hip and with the host
-// simulation (tests/host_sim/sim_mat_ew.cpp), host + device:
-//   * the per-element arithmetic of multiply_complex_exponential (OpMulCexp) and of the wrap-around binary operations
-//     (k_binary_smaller) -- elementwise.hip and mat_ew.hip compile the SAME expressions, so a row of a matrix is
-//     bit-equal to the vector call on that row (both objects are built without FMA contraction);
+// mat_ew_core.h -- what mat_ew.hip shares with the vector unit elementwise.hip and with the host simulation
+// (tests/host_sim/sim_mat_ew.cpp), host + device:
+//   * the per-element arithmetic of multiply_complex_exponential -- elementwise.hip's OpMulCexp (the vector's kernel) and
+//     mat_ew.hip compile the SAME expressions, so a row of a matrix is bit-equal to the vector call on that row (both
+//     objects are built without FMA contraction) -- and of the wrap-around binary operations;
 //   * the lane -> (row, position) map of the shared-phasor mixer k_mw_cexp;
 //   * the flat element walk of k_mw_reverse and k_mw_smaller: one divide per lane, the position in the row, the row and
 //     the operand's period are carried from one grid stride to the next.
@@ -23,7 +23,9 @@
 namespace bdsp {
 
 // ---------------------------------------------------------------------------------------------
-// multiply_complex_exponential (complex_ops.rs:81-105): z[k] *= exp(j (a k + b)), a and b already multiplied by delta
+// multiply_complex_exponential (complex_ops.rs:81-105): z[k] *= exp(j (a k + b)), a and b already multiplied by delta.
+// The reference advances a running product per element, whose error grows with the index; here every position gets its
+// own phase, reduced in double, so the result is at least as close to the exact value (compared with tolerance).
 // ---------------------------------------------------------------------------------------------
 // the phasor of position k: the phase in double, then rounded to T
 template <typename T>

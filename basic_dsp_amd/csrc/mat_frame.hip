@@ -3,8 +3,8 @@
 //   overlap_add   the rows of a matrix summed back into one vector, `hop` apart (the synthesis step)
 //   from_vectors  equally long vectors -> the rows of a matrix (the reference's to_mat,
 //                 matrix/src/to_from_mat_conversions.rs)
-//   zero_pad, swap_halves / fft_shift / ifft_shift of every row (matrix/src/time_freq.rs forwards them row by row; the
-//                 per-row maps are reorg.hip's rg_zero_pad and rg_rotate)
+//   zero_pad, swap_halves / fft_shift / ifft_shift of a vector (data_reorganization.rs:343-442, vector_types/mod.rs:
+//                 171-191) or of every row of a matrix (matrix/src/time_freq.rs forwards them row by row)
 // One launch each, whatever the row count.
 //
 // Every kernel moves whole ELEMENTS (a real scalar or an interleaved complex pair) as one packet of 4 .. 16 bytes, one
@@ -29,7 +29,7 @@ static inline unsigned mf_grid(size_t n)
 }
 
 template <typename T> struct mf_vec2 { typedef T type __attribute__((ext_vector_type(2))); };
-// a whole element as one packet, as reorg.hip's packet_of
+// a whole element as one packet
 template <typename T, int ELEM> struct mf_packet_of { using type = T; };
 template <typename T> struct mf_packet_of<T, 2> { using type = typename mf_vec2<T>::type; };
 

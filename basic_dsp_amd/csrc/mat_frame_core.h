@@ -72,7 +72,7 @@ BDSP_MF_HD void mf_ola_rows(IDX q, IDX rem, IDX rows, IDX F, IDX H, IDX* r0, IDX
     *r0 = q > back ? q - back : 0;
 }
 
-// zero_pad of a row of pb points to `points` (reorg.hip, rg_zero_pad): out = zeros; out[d0 .. d0 + n0) = in[0 ..);
+// zero_pad of a row of pb points to `points` (data_reorganization.rs:343-358, 429-442): out = zeros; out[d0 .. d0 + n0) = in[0 ..);
 // out[d1 .. d1 + n1) = in[s1 ..).  option 0 End, 1 Surround (right = diff / 2), else Center (the first ceil(pb / 2)
 // points stay, the last floor(pb / 2) move to the end).
 template <typename IDX>
@@ -102,7 +102,8 @@ BDSP_MF_HD bool mf_pad_src(IDX g, const MfPad<IDX>& p, IDX* src)
     return false;
 }
 
-// rotate (reorg.hip, k_rotate): out[i] = in[(i + shift) mod points], shift < points
+// rotate: out[i] = in[(i + shift) mod points], shift < points.  fft_shift: shift = ceil(points / 2); ifft_shift: shift =
+// floor(points / 2) -- for odd lengths exactly what the reference's cycle walk produces (KATs vector_types/mod.rs:700-712)
 template <typename IDX>
 BDSP_MF_HD IDX mf_rotate_src(IDX i, IDX points, IDX shift)
 {

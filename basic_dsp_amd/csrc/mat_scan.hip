@@ -1,12 +1,17 @@
-// mat_scan.hip -- diff / diff_with_start, cum_sum and unwrap of every row of a matrix (matrix/src/general/elementary.rs:
-// 206-225 DiffSumOps, matrix/src/real.rs:69-83 ModuloOps), each with a launch count that does not depend on the number
-// of rows.  Every row behaves as the vector function of the same name (vecmath.hip) on that row.
-//   * k_ms_diff: one launch over the flat output.
-//   * k_ms_scan_*: per-row prefix sums, the running sum carried in double and rounded once per element (vm_cum_sum's
-//     semantics).  Rows of at most SCAN_CHUNK points in ONE pass without scratch (a lane group per row, or a workgroup
-//     per row), longer rows in the three steps of vm_cum_sum with the row as a grid dimension.
-//   * k_ms_unwrap: the recurrence cannot be parallelised within a row (vecmath.hip), the rows are independent: one
-//     lane per row, the tiles travel global <-> LDS with coalesced runs (mat_scan_core.h).
+// mat_scan.hip -- cum_sum (diff_sum.rs:110-122) and unwrap (real_ops.rs:262-284) of a vector or of every row of a matrix
+// (a vector is a matrix of one row), and diff / diff_with_start of every row of a matrix (matrix/src/general/
+// elementary.rs:206-225 DiffSumOps, matrix/src/real.rs:69-83 ModuloOps).  The launch counts do not depend on the number
+// of rows.
+//   * k_ms_diff: one launch over the flat output; every row as vecmath.hip's k_diff on it (the vector keeps that kernel:
+//     at 2^20 points it measured faster than this one with one row).
+//   * k_ms_scan_*: per-row prefix sums, the running sum carried in double whatever T is and rounded once per element
+//     (the reference adds sequentially in T; compared with tolerance).  Rows of at most SCAN_CHUNK points in ONE pass
+//     without scratch (a lane group per row, or a workgroup per row), longer rows in three steps with the row as a grid
+//     dimension: chunk sums -> scan of the chunk sums -> rescan of every chunk with its offset.
+//   * k_ms_unwrap: y[j] = F(x[j], y[j-1]) with a data-dependent branch on the ALREADY UNWRAPPED neighbour is a
+//     genuinely sequential recurrence (its state does not reduce to an associative operator), the rows are
+//     independent: one lane per row, the tiles travel global <-> LDS with coalesced runs (mat_scan_core.h).  Exact, not
+//     fast for one long row (see DESIGN.md for the rate).
 #include "bdsp_internal.h"
 #include "mat_scan_core.h"
 
@@ -88,9 +93,10 @@ __global__ __launch_bounds__(256) void k_ms_scan_short(T* __restrict__ x, size_t
     }
 }
 
-// One chunk of SCAN_CHUNK points of a row by one workgroup, as k_scan_apply of vecmath.hip: a thread scans 16
-// CONSECUTIVE points, the chunk travels global <-> LDS with unit stride (point e at LDS slot e + e / 16, so that the
-// per-thread runs start in different banks).  `offset`: the E sums of the row's points before the chunk, or null.
+// One chunk of SCAN_CHUNK points of a row by one workgroup: a thread scans 16 CONSECUTIVE points, the chunk travels
+// global <-> LDS with unit stride (point e at LDS slot e + e / 16, so that the per-thread runs start in different
+// banks; reading the runs straight from global memory -- every lane its own cache line -- measured 511 us for 16M
+// complex f32 points).  `offset`: the E sums of the row's points before the chunk, or null.
 template <typename T, int E>
 __device__ __forceinline__ void ms_scan_chunk(T* __restrict__ xrow, size_t n, size_t base, const double* __restrict__ offset)
 {

@@ -1,19 +1,39 @@
-// mat_scan_core.h -- index math of the per-row unwrap of a matrix (mat_scan.hip, k_ms_unwrap), host + device: which
-// lane loads which element of a tile, where it lands in LDS, which lane walks which row, and the recurrence step.
-// tests/host_sim/sim_mat_scan.cpp drives exactly these functions with threads as loops.
+// mat_scan_core.h -- the scan chunk size, the exact remainder of unwrap's serial chain and the index math of the per-row
+// unwrap (mat_scan.hip, k_ms_unwrap), host + device: which lane loads which element of a tile, where it lands in LDS,
+// which lane walks which row, and the recurrence step.  tests/host_sim/sim_mat_scan.cpp drives exactly these functions
+// with threads as loops, where the device qualifiers fall away.
 #pragma once
 
+#include <math.h>
 #include <stddef.h>
-
-#include "scan_common.h"
 
 #if defined(__HIPCC__)
 #define BDSP_MS_HD __host__ __device__ __forceinline__
+#define BDSP_SCAN_FN __device__ __forceinline__
 #else
 #define BDSP_MS_HD inline
+#define BDSP_SCAN_FN inline
 #endif
 
 namespace bdsp {
+
+constexpr int SCAN_PER_THREAD = 16;
+constexpr int SCAN_CHUNK = 256 * SCAN_PER_THREAD; // elements per workgroup
+
+// fmod on the serial critical path: the remainder a - trunc(a/b)*b is exactly representable, so one fma returns it
+// exactly when the quotient is right; a quotient off by one (a/b rounded across an integer) shows as a remainder
+// outside [0, |b|) and is redone.  Huge quotients, infinities and NaNs go to the library function.
+template <typename T>
+BDSP_SCAN_FN T fmod_exact(T a, T b, T inv_abs_b)
+{
+    const T A = fabs(a), Bv = fabs(b);
+    T q = trunc(A * inv_abs_b); // a guess within one of trunc(A / Bv): the checks below settle it
+    if (!(q < (T)(sizeof(T) == 4 ? 4194304.0 : 2251799813685248.0))) return fmod(a, b);
+    T r = fma(-q, Bv, A);
+    if (r < T(0)) r = fma(-(q - T(1)), Bv, A);
+    else if (r >= Bv) r = fma(-(q + T(1)), Bv, A);
+    return copysign(r, a);
+}
 
 // One wavefront per workgroup.  A workgroup owns R consecutive rows and moves them through LDS in tiles of
 // R rows x W columns, R * W = MS_TILE_BYTES / sizeof(T) elements whatever R is: every one of the 64 lanes loads and
@@ -61,7 +81,7 @@ BDSP_MS_HD int ms_tile_cols(size_t row_len, size_t t, int W)
     return left < (size_t)W ? (int)left : W;
 }
 
-// one step of unwrap (real_ops.rs:262-284), as k_unwrap of vecmath.hip: `prev` is the ALREADY unwrapped neighbour
+// one step of unwrap (real_ops.rs:262-284): `prev` is the ALREADY unwrapped neighbour
 template <typename T>
 BDSP_SCAN_FN T ms_unwrap_step(T cur, T prev, T half, T divisor, T inv)
 {

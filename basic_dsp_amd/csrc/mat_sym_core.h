@@ -46,7 +46,7 @@ BDSP_SY_HD IDX sy_crop_src(IDX row, IDX j, IDX n) { return row * n + j; }
 
 // mirror (freq.rs:52-83) of the half spectrum h(j) = in[(j + rot) mod p], rot < p: output position g < 2p - 1 reads bin
 // sy_mirror_bin of its row, conjugated if *conj.  rot = 0: the plain mirror; rot = p / 2: ifft_shift of the half
-// spectrum first (out[i] = in[(i + p/2) mod p], reorg.hip k_rotate).
+// spectrum first (out[i] = in[(i + p/2) mod p], mat_frame_core.h mf_rotate_src).
 template <typename IDX>
 BDSP_SY_HD IDX sy_mirror_bin(IDX g, IDX p, IDX rot, bool* conj)
 {

@@ -1,9 +1,8 @@
-// reorg.hip -- pure index moves (bit-exact): swap_halves / fft_shift / ifft_shift, reverse,
-// zero_pad, zero_interleave, mirror.  All out-of-place (the handle trades buffers afterwards, like
-// the reference's Buffer::trade, vector/src/vector_types/support_std.rs:78-82).
-//   swap_array_halves   vector/src/vector_types/mod.rs:171-191
-//   reverse / zero_pad / zero_interleave   vector/src/vector_types/general/data_reorganization.rs:237-479
-//   mirror              vector/src/vector_types/time_freq/freq.rs:52-83
+// reorg.hip -- pure index moves (bit-exact): zero_interleave, decimatei and the circular extension of the long-filter
+// convolution.  All out-of-place (the handle trades buffers afterwards, like the reference's Buffer::trade,
+// vector/src/vector_types/support_std.rs:78-82).  The moves that know rows -- swap_halves / fft_shift / ifft_shift,
+// zero_pad, reverse, mirror -- serve vectors and matrices alike from mat_frame.hip, mat_ew.hip and mat_sym.hip.
+//   zero_interleave   vector/src/vector_types/general/data_reorganization.rs:237-479
 #include "bdsp_internal.h"
 
 namespace bdsp {
@@ -23,39 +22,6 @@ template <typename T, int ELEM> struct packet_of { using type = T; };
 template <typename T> struct packet_of<T, 2> { using type = cpx<T>; };
 
 template <typename P> __device__ __forceinline__ P zero_packet() { P z; __builtin_memset(&z, 0, sizeof(P)); return z; }
-
-// out[i] = in[(i + shift) mod points].
-// fft_shift: shift = ceil(points/2); ifft_shift: shift = floor(points/2) -- for odd lengths this is
-// exactly what the reference's cycle walk produces (KATs vector_types/mod.rs:700-712).
-template <typename P, typename IDX>
-__global__ __launch_bounds__(256) void k_rotate(const P* __restrict__ in, P* __restrict__ out, IDX points, IDX shift)
-{
-    for (IDX i = (IDX)blockIdx.x * blockDim.x + threadIdx.x; i < points; i += (IDX)gridDim.x * blockDim.x) {
-        IDX src = i + shift;
-        if (src >= points) src -= points;
-        out[i] = in[src];
-    }
-}
-
-template <typename P, typename IDX>
-__global__ __launch_bounds__(256) void k_reverse(const P* __restrict__ in, P* __restrict__ out, IDX points)
-{
-    for (IDX i = (IDX)blockIdx.x * blockDim.x + threadIdx.x; i < points; i += (IDX)gridDim.x * blockDim.x)
-        out[i] = in[points - 1 - i];
-}
-
-// out = zeros(len); out[dst0 .. dst0+n0) = in[src0 ..); out[dst1 .. dst1+n1) = in[src1 ..)   (in elements)
-template <typename P, typename IDX>
-__global__ __launch_bounds__(256) void k_two_segment_copy(const P* __restrict__ in, P* __restrict__ out, IDX len,
-                                                           IDX dst0, IDX src0, IDX n0, IDX dst1, IDX src1, IDX n1)
-{
-    for (IDX g = (IDX)blockIdx.x * blockDim.x + threadIdx.x; g < len; g += (IDX)gridDim.x * blockDim.x) {
-        P v = zero_packet<P>();
-        if (g >= dst0 && g - dst0 < n0) v = in[src0 + (g - dst0)];
-        else if (g >= dst1 && g - dst1 < n1) v = in[src1 + (g - dst1)];
-        out[g] = v;
-    }
-}
 
 // out[i*factor] = in[i], zero elsewhere (one thread per OUTPUT element: contiguous stores)
 template <typename P, typename IDX>
@@ -88,21 +54,6 @@ __global__ __launch_bounds__(256) void k_zero_interleave2(const P* __restrict__ 
     } else {
         for (IDX i = (IDX)blockIdx.x * blockDim.x + threadIdx.x; i < points; i += (IDX)gridDim.x * blockDim.x)
             o2[i] = P2{in[i], zero_packet<P>()};
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void k_mirror(const cpx<T>* __restrict__ in, cpx<T>* __restrict__ out,
-                                                 size_t p)
-{
-    size_t total = 2 * p - 1;
-    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < total;
-         g += (size_t)gridDim.x * blockDim.x) {
-        if (g < p) out[g] = in[g];
-        else {
-            cpx<T> z = in[2 * p - 1 - g]; // g = p-1+k  ->  in[p-k]
-            out[g] = cpx<T>{z.x, -z.y};
-        }
     }
 }
 
@@ -160,44 +111,6 @@ template <typename T> int rg_wrap_copy(const T* in, T* out, size_t points, size_
 #undef BDSP_RG_ARGS
     return BDSP_OK;
 }
-template <typename T> int rg_rotate(const T* in, T* out, size_t points, size_t elem, size_t shift, hipStream_t s)
-{
-    if (points == 0) return BDSP_OK;
-    const size_t sh = shift % points;
-#define BDSP_RG_ARGS(P, I) reinterpret_cast<const P*>(in), reinterpret_cast<P*>(out), (I)points, (I)sh
-    BDSP_RG_LAUNCH(k_rotate, 2 * points);
-#undef BDSP_RG_ARGS
-    return BDSP_OK;
-}
-template <typename T> int rg_reverse(const T* in, T* out, size_t points, size_t elem, hipStream_t s)
-{
-    if (points == 0) return BDSP_OK;
-#define BDSP_RG_ARGS(P, I) reinterpret_cast<const P*>(in), reinterpret_cast<P*>(out), (I)points
-    BDSP_RG_LAUNCH(k_reverse, points);
-#undef BDSP_RG_ARGS
-    return BDSP_OK;
-}
-// option: 0 End, 1 Surround (zero_pad_b flavour: right = diff/2, data_reorganization.rs:429-442),
-// 2 Center (first ceil(P/2) points stay, last floor(P/2) move to the end, :343-358).
-template <typename T> int rg_zero_pad(const T* in, T* out, size_t len_before, bool is_complex, size_t points, int option, hipStream_t s)
-{
-    const size_t elem = is_complex ? 2 : 1, len = points * elem;
-    if (len <= len_before) return BDSP_ERR_ARG_LENGTH;
-    const size_t pb = len_before / elem; // all offsets below are in ELEMENTS
-    size_t d0 = 0, s0 = 0, n0 = pb, d1 = 0, s1 = 0, n1 = 0;
-    if (option == 1) {
-        size_t diff = points - pb, right = diff / 2;
-        d0 = diff - right;
-    } else if (option != 0) {
-        size_t right = pb / 2, left = pb - pb / 2;
-        n0 = left;
-        d1 = points - right; s1 = pb - right; n1 = right;
-    }
-#define BDSP_RG_ARGS(P, I) reinterpret_cast<const P*>(in), reinterpret_cast<P*>(out), (I)points, (I)d0, (I)s0, (I)n0, (I)d1, (I)s1, (I)n1
-    BDSP_RG_LAUNCH(k_two_segment_copy, points);
-#undef BDSP_RG_ARGS
-    return BDSP_OK;
-}
 template <typename T> int rg_zero_interleave(const T* in, T* out, size_t len, size_t elem, size_t factor, hipStream_t s)
 {
     if (len == 0) return BDSP_OK;
@@ -213,23 +126,9 @@ template <typename T> int rg_zero_interleave(const T* in, T* out, size_t len, si
 #undef BDSP_RG_ARGS
     return BDSP_OK;
 }
-template <typename T> int rg_mirror(const T* in, T* out, size_t len, hipStream_t s)
-{
-    size_t p = len / 2;
-    if (p == 0) return BDSP_OK;
-    hipLaunchKernelGGL((k_mirror<T>), dim3(rg_grid(2 * p)), dim3(256), 0, s,
-                       reinterpret_cast<const cpx<T>*>(in), reinterpret_cast<cpx<T>*>(out), p);
-    BDSP_LAUNCH_CHECK();
-    return BDSP_OK;
-}
-
 #define BDSP_INST(T)                                                                               \
-    template int rg_rotate<T>(const T*, T*, size_t, size_t, size_t, hipStream_t);                  \
     template int rg_wrap_copy<T>(const T*, T*, size_t, size_t, size_t, long long, hipStream_t);    \
-    template int rg_reverse<T>(const T*, T*, size_t, size_t, hipStream_t);                         \
-    template int rg_zero_pad<T>(const T*, T*, size_t, bool, size_t, int, hipStream_t);             \
     template int rg_zero_interleave<T>(const T*, T*, size_t, size_t, size_t, hipStream_t);         \
-    template int rg_mirror<T>(const T*, T*, size_t, hipStream_t);                                  \
     template int rg_decimate<T>(const T*, T*, size_t, size_t, size_t, size_t, hipStream_t);
 BDSP_INST(float)
 BDSP_INST(double)

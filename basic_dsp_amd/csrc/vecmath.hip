@@ -1,7 +1,7 @@
 // vecmath.hip -- the facade's remaining per-element families, device resident:
 //   * TrigOps / PowerOps / abs / wrap / the "approximated" ops (trigonometry_and_powers.rs:196-420,
 //     real_ops.rs:236-375) as one in-place packet map,
-//   * diff / diff_with_start / cum_sum (diff_sum.rs:65-122), unwrap (real_ops.rs:262-284),
+//   * diff / diff_with_start of a vector (diff_sum.rs:65-108; cum_sum and unwrap: mat_scan.hip),
 //   * get/set real_imag and mag_phase (complex_to_real.rs:674-770), split_into / merge
 //     (data_reorganization.rs:484-555).
 // The complex functions restate num-complex 0.4's formulas (polar forms of sqrt/powf/ln/log/expf, logarithmic
@@ -9,7 +9,6 @@
 // from the reference is only the last-ulp behaviour of the math library underneath.
 #include "bdsp_internal.h"
 #include "ew_map.h"
-#include "scan_common.h"
 
 namespace bdsp {
 
@@ -228,175 +227,6 @@ template <typename T> int vm_diff(const T* in, T* out, size_t n_out, size_t step
     return BDSP_OK;
 }
 
-// ---- cum_sum: chunk sums -> scan of the chunk sums -> rescan of every chunk with its offset ---------------------
-// The running sum is carried in double whatever T is (the reference adds sequentially in T; the result here is the
-// correctly rounded-once prefix, compared with tolerance).  E interleaved sequences (1 real, 2 complex).
-// (SCAN_PER_THREAD, SCAN_CHUNK: scan_common.h, shared with the per-row scans of mat_scan.hip)
-
-// chunk sums: order does not matter, so the chunk is read with unit stride across the workgroup
-template <typename T, int E>
-__global__ __launch_bounds__(256) void k_scan_sums(const T* __restrict__ x, size_t n, double* __restrict__ sums)
-{
-    __shared__ double sh[E][256];
-    const size_t base = (size_t)blockIdx.x * SCAN_CHUNK;
-    double acc[E] = {};
-    for (int k = 0; k < SCAN_PER_THREAD; ++k) {
-        const size_t i = base + (size_t)k * 256 + threadIdx.x;
-        if (i < n)
-            for (int c = 0; c < E; ++c) acc[c] += (double)x[i * E + c];
-    }
-    for (int c = 0; c < E; ++c) sh[c][threadIdx.x] = acc[c];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s)
-            for (int c = 0; c < E; ++c) sh[c][threadIdx.x] += sh[c][threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0)
-        for (int c = 0; c < E; ++c) sums[(size_t)blockIdx.x * E + c] = sh[c][0];
-}
-
-// exclusive scan of the chunk sums by one workgroup (each thread owns a contiguous run)
-template <int E>
-__global__ __launch_bounds__(256) void k_scan_offsets(double* __restrict__ sums, size_t nchunks)
-{
-    __shared__ double sh[E][256];
-    const size_t per = (nchunks + 255) / 256, b = threadIdx.x * per, e = b + per < nchunks ? b + per : nchunks;
-    double acc[E] = {};
-    for (size_t i = b; i < e; ++i)
-        for (int c = 0; c < E; ++c) acc[c] += sums[i * E + c];
-    for (int c = 0; c < E; ++c) sh[c][threadIdx.x] = acc[c];
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int c = 0; c < E; ++c) {
-            double run = 0.0;
-            for (int t = 0; t < 256; ++t) { const double v = sh[c][t]; sh[c][t] = run; run += v; }
-        }
-    __syncthreads();
-    double run[E];
-    for (int c = 0; c < E; ++c) run[c] = sh[c][threadIdx.x];
-    for (size_t i = b; i < e; ++i)
-        for (int c = 0; c < E; ++c) { const double v = sums[i * E + c]; sums[i * E + c] = run[c]; run[c] += v; }
-}
-
-// A thread scans 16 CONSECUTIVE elements; the chunk travels global <-> LDS with unit stride across the workgroup
-// (element e lives at LDS slot e + e/16, so the per-thread runs start in different banks).  Reading the runs
-// straight from global memory -- every lane its own cache line -- measured 511 us for 16M complex f32 points.
-template <typename T, int E>
-__global__ __launch_bounds__(256) void k_scan_apply(T* __restrict__ x, size_t n, const double* __restrict__ offsets)
-{
-    struct El { T c[E]; };
-    __shared__ El tile[SCAN_CHUNK + SCAN_CHUNK / 16];
-    __shared__ double sh[E][256];
-    const size_t base = (size_t)blockIdx.x * SCAN_CHUNK;
-    El* xe = reinterpret_cast<El*>(x);
-    for (int k = 0; k < SCAN_PER_THREAD; ++k) {
-        const int e = k * 256 + threadIdx.x;
-        El v;
-        for (int c = 0; c < E; ++c) v.c[c] = T(0);
-        if (base + e < n) v = xe[base + e];
-        tile[e + (e >> 4)] = v;
-    }
-    __syncthreads();
-    double v[SCAN_PER_THREAD][E];
-    double acc[E] = {};
-    for (int k = 0; k < SCAN_PER_THREAD; ++k) {
-        const El el = tile[threadIdx.x * 17 + k];
-        for (int c = 0; c < E; ++c) { v[k][c] = (double)el.c[c]; acc[c] += v[k][c]; }
-    }
-    for (int c = 0; c < E; ++c) sh[c][threadIdx.x] = acc[c];
-    __syncthreads();
-    // Hillis-Steele inclusive scan of the 256 thread totals
-    for (int d = 1; d < 256; d <<= 1) {
-        double t[E];
-        for (int c = 0; c < E; ++c) t[c] = (int)threadIdx.x >= d ? sh[c][threadIdx.x - d] : 0.0;
-        __syncthreads();
-        for (int c = 0; c < E; ++c) sh[c][threadIdx.x] += t[c];
-        __syncthreads();
-    }
-    double run[E];
-    for (int c = 0; c < E; ++c) run[c] = offsets[(size_t)blockIdx.x * E + c] + (threadIdx.x ? sh[c][threadIdx.x - 1] : 0.0);
-    for (int k = 0; k < SCAN_PER_THREAD; ++k) {
-        El el;
-        for (int c = 0; c < E; ++c) { run[c] += v[k][c]; el.c[c] = (T)run[c]; }
-        tile[threadIdx.x * 17 + k] = el;
-    }
-    __syncthreads();
-    for (int k = 0; k < SCAN_PER_THREAD; ++k) {
-        const int e = k * 256 + threadIdx.x;
-        if (base + e < n) xe[base + e] = tile[e + (e >> 4)];
-    }
-}
-
-// `scratch` holds E doubles per chunk of SCAN_CHUNK elements
-template <typename T> size_t vm_cum_sum_scratch(size_t len, bool is_complex)
-{
-    const size_t n = is_complex ? len / 2 : len;
-    return sizeof(double) * 2 * ((n + SCAN_CHUNK - 1) / SCAN_CHUNK + 1);
-}
-template <typename T> int vm_cum_sum(T* x, size_t len, bool is_complex, void* scratch, hipStream_t s)
-{
-    const size_t n = is_complex ? len / 2 : len;
-    if (n == 0) return BDSP_OK;
-    const size_t nchunks = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    double* sums = static_cast<double*>(scratch);
-    if (is_complex) {
-        hipLaunchKernelGGL((k_scan_sums<T, 2>), dim3((unsigned)nchunks), dim3(256), 0, s, x, n, sums);
-        hipLaunchKernelGGL((k_scan_offsets<2>), dim3(1), dim3(256), 0, s, sums, nchunks);
-        hipLaunchKernelGGL((k_scan_apply<T, 2>), dim3((unsigned)nchunks), dim3(256), 0, s, x, n, sums);
-    } else {
-        hipLaunchKernelGGL((k_scan_sums<T, 1>), dim3((unsigned)nchunks), dim3(256), 0, s, x, n, sums);
-        hipLaunchKernelGGL((k_scan_offsets<1>), dim3(1), dim3(256), 0, s, sums, nchunks);
-        hipLaunchKernelGGL((k_scan_apply<T, 1>), dim3((unsigned)nchunks), dim3(256), 0, s, x, n, sums);
-    }
-    BDSP_LAUNCH_CHECK();
-    return BDSP_OK;
-}
-
-// ---- unwrap (real_ops.rs:262-284) --------------------------------------------------------------------------------
-// y[j] = F(x[j], y[j-1]) with a data-dependent branch on the ALREADY UNWRAPPED neighbour: a genuinely sequential
-// recurrence (its state does not reduce to an associative operator), so one lane walks the vector while the
-// wavefront stages tiles through LDS with coalesced packets.  Exact, not fast (see DESIGN.md for the rate).
-// fmod_exact, the remainder on the serial critical path: scan_common.h (mat_scan.hip compiles the same function).
-template <typename T>
-__global__ __launch_bounds__(64) void k_unwrap(T* __restrict__ x, size_t len, T divisor)
-{
-    constexpr int TILE = 2048;
-    __shared__ T tin[TILE];
-    __shared__ T tout[TILE]; // a second array: the walker's reads never wait for its own writes
-    const T half = divisor / T(2);
-    const T inv = T(1) / fabs(divisor);
-    T prev = T(0);
-    for (size_t base = 0; base < len; base += TILE) {
-        const int m = len - base < (size_t)TILE ? (int)(len - base) : TILE;
-        for (int i = threadIdx.x; i < m; i += 64) tin[i] = x[base + i];
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int j = 0;
-            if (base == 0) { prev = tin[0]; tout[0] = prev; j = 1; }
-#pragma unroll 8
-            for (; j < m; ++j) {
-                T cur = tin[j];
-                T diff = cur - prev;
-                if (diff > half) { diff = fmod_exact(diff, divisor, inv); diff = diff - divisor; cur = prev + diff; }
-                else if (diff < -half) { diff = fmod_exact(diff, divisor, inv); diff = diff + divisor; cur = prev + diff; }
-                tout[j] = cur;
-                prev = cur;
-            }
-        }
-        __syncthreads();
-        for (int i = threadIdx.x; i < m; i += 64) x[base + i] = tout[i];
-        __syncthreads();
-    }
-}
-template <typename T> int vm_unwrap(T* x, size_t len, T divisor, hipStream_t s)
-{
-    if (len < 2) return BDSP_OK;
-    hipLaunchKernelGGL(k_unwrap<T>, dim3(1), dim3(64), 0, s, x, len, divisor);
-    BDSP_LAUNCH_CHECK();
-    return BDSP_OK;
-}
-
 // ---- real/imag and magnitude/phase pairs ------------------------------------------------------------------------
 // kind 0: (re, im) -> a, b   kind 1: (|z|, arg z) -> a, b   (to_polar = (hypot, atan2))
 template <typename T>
@@ -461,9 +291,6 @@ template <typename T> int vm_split_merge(T* whole, T* const* parts_dev, size_t l
 #define BDSP_INST(T)                                                                                   \
     template int ew_math<T>(T*, size_t, bool, int, T, hipStream_t);                                    \
     template int vm_diff<T>(const T*, T*, size_t, size_t, bool, hipStream_t);                          \
-    template size_t vm_cum_sum_scratch<T>(size_t, bool);                                               \
-    template int vm_cum_sum<T>(T*, size_t, bool, void*, hipStream_t);                                  \
-    template int vm_unwrap<T>(T*, size_t, T, hipStream_t);                                             \
     template int vm_complex_split<T>(const T*, T*, T*, size_t, int, hipStream_t);                      \
     template int vm_complex_join<T>(T*, const T*, const T*, size_t, int, hipStream_t);                 \
     template int vm_split_merge<T>(T*, T* const*, size_t, bool, size_t, bool, hipStream_t);

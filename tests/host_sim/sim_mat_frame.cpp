@@ -10,8 +10,8 @@
 //                 row order against the row loop y[r * H .. r * H + F) += m[r], bit for bit
 //   from_vectors  rows 1..5 x points 1..9
 //   zero_pad, rotate   row points 1..70, 127..129, 1023..1025, rows 1, 2, 3; End / Surround / Center to one point more,
-//                 to 2n and to 2n + 3; rotations by ceil(n / 2) and floor(n / 2): equal to the per-row maps of reorg.hip
-//                 (restated here: k_two_segment_copy with rg_zero_pad's segments, k_rotate)
+//                 to 2n and to 2n + 3; rotations by ceil(n / 2) and floor(n / 2): equal to the per-row maps, restated
+//                 here on their own (two copied segments over zeros; out[i] = in[(i + shift) mod n])
 //   maps only     one extent pair above 2^32: positions, advance and sources with 64-bit indices
 //
 // Grids are chosen so that lanes run zero, one and several trips and the stride is smaller than, equal to and larger
@@ -200,9 +200,9 @@ static void vectors_case(size_t rows, size_t points)
 }
 
 // ---------------------------------------------------------------------------------------------
-// zero_pad and rotate against the per-row maps of reorg.hip
+// zero_pad and rotate against the per-row maps, restated without the core header
 // ---------------------------------------------------------------------------------------------
-// rg_zero_pad's segments and k_two_segment_copy's rule, restated
+// zero_pad's two segments (End, Surround: right = diff / 2, Center) and the copy rule, restated
 static void ref_zero_pad_row(const double* in, double* out, size_t pb, size_t points, int option)
 {
     size_t d0 = 0, s0 = 0, n0 = pb, d1 = 0, s1 = 0, n1 = 0;
@@ -254,7 +254,7 @@ static void moves_case(size_t rows, size_t n, const unsigned* g)
         });
         check_written_once(writes, "rotate", rows, n, shift);
         for (size_t r = 0; r < rows; ++r)
-            for (size_t i = 0; i < n; ++i) { // k_rotate on row r
+            for (size_t i = 0; i < n; ++i) { // the rotation of row r
                 size_t src = i + sh;
                 if (src >= n) src -= n;
                 EXPECT(out[r * n + i] == in[r * n + src], "rotate %zu x %zu by %zu: row %zu point %zu", rows, n, shift, r, i);

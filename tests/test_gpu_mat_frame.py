@@ -254,7 +254,7 @@ def test_frame_codes(bd, dtype, cplx):
 
 # ---------------------------------------------------------------------------------------------- batched index moves
 def _pad_ref(x, e, p, points, option):
-    """rg_zero_pad per row: End, Surround (right = diff // 2), Center (the first ceil(p / 2) points stay, the last
+    """zero_pad per row: End, Surround (right = diff // 2), Center (the first ceil(p / 2) points stay, the last
     floor(p / 2) move to the end)"""
     rows = x.shape[0]
     pts = x.reshape(rows, p, e)

@@ -9,7 +9,7 @@ import oracle_lib as orc
 pytestmark = pytest.mark.gpu
 
 DTYPES = (np.float32, np.float64)
-SCAN_CHUNK = 4096      # scan_common.h
+SCAN_CHUNK = 4096      # mat_scan_core.h
 SCAN_SHORT = 512       # mat_scan.hip MS_SCAN_SHORT: a lane group per row up to here, then a workgroup per row
 TILE_BYTES = 16384     # mat_scan_core.h MS_TILE_BYTES
 
@@ -65,7 +65,7 @@ def test_diff_rows_equal_the_oracle(bd, dtype, cplx):
             got = m.data()
             if rows * pts == 0:
                 continue
-            # k_diff's arithmetic is one subtraction per element: the oracle's, vectorised over the rows ...
+            # diff's arithmetic is one subtraction per element: the oracle's, vectorised over the rows ...
             ref = x.copy() if with_start else x[:, e:] - x[:, :-e]
             if with_start:
                 ref[:, e:] = x[:, e:] - x[:, :-e]
@@ -125,8 +125,8 @@ def test_wrap_equals_the_oracle_on_the_flat_data(bd, dtype):
 
 
 def _chain(n):
-    """Longest chain of double additions between an input and an output of the three-step scan (vm_cum_sum of
-    vecmath.hip, and mat_scan.hip's long rows), counted from the code: chunk sums 16 per thread + 8 tree levels;
+    """Longest chain of double additions between an input and an output of the three-step scan (mat_scan.hip's long
+    rows, and a long vector), counted from the code: chunk sums 16 per thread + 8 tree levels;
     offsets 2 * ceil(nchunks / 256) per thread + the 256-step serial scan; apply 16 thread total + 8 Hillis-Steele
     + 1 offset + 16 running.  mat_scan.hip's one-pass regimes are shorter (lane groups: 6 shuffle steps + at most 8
     carries; workgroup per row: the 41 of apply), so the same count bounds them."""

@@ -24,7 +24,8 @@ PARTS = ("get_real", "get_imag", "get_magnitude", "get_magnitude_squared", "get_
          "set_real_imag", "set_mag_phase")
 ENTRIES = MATH0 + MATH1 + ROW_AWARE + PARTS
 METHODS = MATH0 + MATH1 + ("reverse", "multiply_complex_exponential") + SMALLER + PARTS
-HOST_FUNCTIONS = ("mat_reverse", "mat_mul_cexp", "mat_smaller", "mat_smaller_vector", "mat_get_part", "mat_get_pair",
+ROW_HOST_FUNCTIONS = ("op_reverse",)  # one body for vectors and matrices (rows = 1 by default)
+HOST_FUNCTIONS = ("mat_mul_cexp", "mat_smaller", "mat_smaller_vector", "mat_get_part", "mat_get_pair",
                   "mat_set_pair")
 
 
@@ -73,11 +74,12 @@ def test_python_binds_the_methods():
 
 
 def test_no_row_loop_and_no_synchronise_in_the_new_host_functions():
-    """mat_reverse .. mat_set_pair use neither mat_each_row nor mat_resize_rows, no loop at all and no stream or device
-    synchronise; the math family is op_math on the flat vector; the launchers of mat_ew.hip hold no loop either"""
+    """op_reverse and mat_mul_cexp .. mat_set_pair use neither mat_each_row nor mat_resize_rows, no loop at
+    all and no stream or device synchronise; the math family is op_math on the flat vector; the launchers of mat_ew.hip
+    hold no loop either"""
     with open(os.path.join(CSRC, "capi.cpp")) as f:
         src = f.read()
-    start = src.index("int mat_reverse(")
+    start = src.index("int mat_mul_cexp(")
     end = src.index("} // namespace", start)
     body = src[start:end]
     for n in HOST_FUNCTIONS:
@@ -85,7 +87,16 @@ def test_no_row_loop_and_no_synchronise_in_the_new_host_functions():
     banned = ("mat_each_row", "mat_resize_rows", "hipStreamSynchronize", "hipDeviceSynchronize")
     assert not [b for b in banned if b in body]
     assert not re.search(r"\b(for|while)\s*\(", body)
+    # reverse: the vector's host function, which takes the matrix's rows
+    start = src.index("int op_reverse(")
+    shared = src[start:src.index("\ntemplate <", start)]
+    for n in ROW_HOST_FUNCTIONS:
+        assert "int %s(" % n in shared and "size_t rows = 1)" in shared[shared.index("int %s(" % n):].split("\n")[0], n
+    assert "mw_reverse<T>(" in shared
+    assert not [b for b in banned if b in shared]
+    assert not re.search(r"\b(for|while)\s*\(", shared)
     entries = src[src.index("#define BDSP_MAT_EW_M0("):src.index("#undef BDSP_MAT_EW\n")]
+    assert "op_reverse<T>(&a->v, a->rows)" in entries
     assert entries.count("op_math<T>(&a->v") == 3  # the two macros of the family and root
     assert not [b for b in banned if b in entries] and not re.search(r"\b(for|while)\s*\(", entries)
     with open(os.path.join(CSRC, "mat_ew.hip")) as f:
@@ -99,8 +110,9 @@ def test_no_row_loop_and_no_synchronise_in_the_new_host_functions():
 
 
 def test_elementwise_hip_shares_the_arithmetic_with_the_matrix_unit():
-    """one definition of OpMulCexp's and k_binary_smaller's per-element expressions, compiled by both units without FMA
-    contraction"""
+    """one definition of OpMulCexp's per-element expressions, compiled by both units without FMA contraction; the
+    *_smaller expressions have one user, mat_ew.hip (vectors run its kernel with one row), and elementwise.hip keeps no
+    copy and no kernel of them"""
     with open(os.path.join(CSRC, "elementwise.hip")) as f:
         vec = f.read()
     with open(os.path.join(CSRC, "mat_ew.hip")) as f:
@@ -110,11 +122,14 @@ def test_elementwise_hip_shares_the_arithmetic_with_the_matrix_unit():
     with open(os.path.join(CSRC, "Makefile")) as f:
         mk = f.read()
     for name in ("cexp_phasor<T>(", "cexp_mul<T>(", "smaller_real<T>(", "smaller_complex<T>("):
-        assert name in vec and name in mat, name
+        if name.startswith("cexp"):
+            assert name in vec and name in mat, name
+        else:   # one copy left: nothing to keep equal
+            assert name in mat and name not in vec, name
         assert re.search(r"BDSP_MW_HD \w+ %s\(" % name[:-4], core), name
     assert '#include "mat_ew_core.h"' in vec and '#include "mat_ew_core.h"' in mat
     # the vector unit keeps no second copy of the expressions
-    assert "sincos(p.a" not in vec and "ar * br - ai * bi" not in vec[vec.index("k_binary_smaller"):]
+    assert "sincos(p.a" not in vec and "k_binary_smaller" not in vec
     for obj in ("elementwise.o", "mat_ew.o"):
         rule = re.search(r"\$\(BUILD\)/%s:[^\n]*\n\t([^\n]*)" % re.escape(obj), mk)
         assert rule and "$(EXACT)" in rule.group(1), obj

@@ -74,14 +74,14 @@ def test_python_binds_the_methods():
 
 
 def test_no_row_loop_and_no_synchronise_in_the_host_functions():
-    """mat_swap, mat_zero_pad, mat_from_frames, mat_overlap_add and mat_from_vectors use neither mat_each_row nor
+    """op_swap (the host function of the shifts, for vectors and matrices), mat_zero_pad, mat_from_frames, mat_overlap_add and mat_from_vectors use neither mat_each_row nor
     mat_resize_rows and no stream or device synchronise.  The one exception: mat_from_vectors uploads its pointer table
     with upload_parts, which waits for that copy (as split_into and merge do) -- that helper holds the call's only
     synchronisation, and the host loop of mat_from_vectors only reads the handles' metadata."""
     with open(os.path.join(CSRC, "capi.cpp")) as f:
         src = f.read()
     banned = ("mat_each_row", "mat_resize_rows", "hipStreamSynchronize", "hipDeviceSynchronize")
-    for n in ("mat_swap", "mat_zero_pad", "mat_from_frames", "mat_overlap_add", "mat_from_vectors"):
+    for n in ("op_swap", "mat_zero_pad", "mat_from_frames", "mat_overlap_add", "mat_from_vectors"):
         body = _host_function(src, n)
         assert len(body) > 100, n
         assert not [b for b in banned if b in body], n
@@ -93,7 +93,7 @@ def test_no_row_loop_and_no_synchronise_in_the_host_functions():
     loop = body[body.index("for ("):body.index("if (count)")]
     assert "hip" not in loop and "mf_" not in loop and "reserve" not in loop
     assert _host_function(src, "upload_parts").count("hipStreamSynchronize") == 1
-    assert "mf_rotate<T>(" in _host_function(src, "mat_swap") and "mf_zero_pad<T>(" in _host_function(src, "mat_zero_pad")
+    assert "mf_rotate<T>(" in _host_function(src, "op_swap") and "mf_zero_pad<T>(" in _host_function(src, "mat_zero_pad")
     entries = src[src.index("#define BDSP_MAT_FRAME("):src.index("#undef BDSP_MAT_FRAME\n")]
     assert not [b for b in banned if b in entries] and not re.search(r"\b(for|while)\s*\(", entries)
     # the launchers of the unit hold no loop and no synchronisation either; the kernels' loops live in the core header

@@ -38,7 +38,7 @@ def test_python_binds_the_methods():
 
 
 def test_mat_scan_and_vecmath_build_without_warnings(tmp_path):
-    """The new unit and the vector unit that now shares scan_common.h, compiled with the Makefile's flags."""
+    """The scan unit (vectors and matrices) and the vector unit of the math family, compiled with the Makefile's flags."""
     if not os.path.exists("/opt/rocm/bin/hipcc"):
         pytest.skip("hipcc not found")
     build = str(tmp_path / "b")
