@@ -277,6 +277,8 @@ for _s, _t, _R in (("32", _F, VectorInteropResult32), ("64", _D, VectorInteropRe
     _proto(_m + "zero_pad" + _s, C.c_int32, _P, _SZ, C.c_int32)
     _proto(_m + "convolve_signal_mat" + _s, C.c_int32, _P, C.POINTER(_P), _SZ)
     _proto(_m + "interpolatef" + _s, C.c_int32, _P, C.c_int32, _t, _t, _t, _SZ)
+    if hasattr(lib, _m + "interpolatef_delays" + _s):  # (an older build named by BDSP_HIP_LIBRARY for an A/B run has none)
+        _proto(_m + "interpolatef_delays" + _s, C.c_int32, _P, C.c_int32, _t, _t, C.POINTER(_t), _SZ, _SZ)
     _proto(_m + "multiply_frequency_response" + _s, C.c_int32, _P, C.c_int32, _t, _t)
     # per-row statistics, sums, dot products: (matrix, out array, out length[, split length])
     for _n, _o in (("real_statistics", _ST), ("complex_statistics", _CST), ("real_statistics_prec", Statistics64),

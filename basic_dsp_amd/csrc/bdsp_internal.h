@@ -187,6 +187,17 @@ int interpolatef_dev(const T* in, T* out, size_t len, bool is_complex, int fid, 
                      T delay, size_t conv_len, T delta, hipStream_t s,
                      T (*host_fn)(const void*, T) = nullptr, const void* host_fn_data = nullptr);
 template <typename T> size_t interpolatef_new_len(size_t len, T factor);
+// what row r of mat_interpolatef_dev takes instead of kernel arguments when every row has a delay of its own: the delay
+// (already divided by the matrix's delta) and frac_slow_pairs of it
+template <typename T>
+struct InterpRowPrm {
+    T delay;
+    unsigned long long slow_pairs;
+};
+unsigned long long frac_slow_pairs(size_t conv_len, double delay, int fid, double rolloff); // conv_len as clipped to points / 2
+template <typename T>
+int mat_interpolatef_dev(const T* in, T* out, size_t rows, size_t row_len, bool is_complex, int fid, T rolloff, T factor,
+                         T delay, const InterpRowPrm<T>* prm, size_t conv_len, T delta, hipStream_t s);
 template <typename T> int conv_function_taps(T* taps, size_t conv_len, int fid, T rolloff, T ratio, int stride, bool reversed, hipStream_t s);
 template <typename T> int conv_function_direct(const T* in, T* out, size_t points, bool is_complex, const T* taps, size_t conv_len, hipStream_t s,
                                                    bool complex_taps = false);

@@ -1757,7 +1757,7 @@ int dot(const DevVec<T>* v, const DevVec<T>* o, bool cplx, double* re, double* i
 // ----------------------------------------------------------------------------------------------
 // Matrix / batch API: `rows` equally long vectors back to back in ONE allocation; a row may start at any
 // scalar, so nothing here may assume a 16-byte aligned row.  Operations are batched launches over all rows
-// except interpolatef (through mat_resize_rows) and the MIMO convolution (one launch per row).  Mirrors
+// except the MIMO convolution, the only per-row launcher (one launch per pair of rows).  Mirrors
 // the matrix crate (matrix/src/lib.rs:195-208 applies an operation to the rows one after the other;
 // matrix/src/time_freq.rs:49-530 forwards the time/frequency traits row by row) -- here the row loop is
 // the grid's batch dimension.
@@ -1791,19 +1791,6 @@ template <typename T> int mat_code(DevMat<T>* m, int code)
 {
     if (code == BDSP_OK && m->v.erroneous()) return BDSP_ERR_POISONED;
     return code;
-}
-
-// rows change length: fn(in_row, out_row) writes new_len scalars per row into the trade buffer
-template <typename T, class F>
-int mat_resize_rows(DevMat<T>* m, size_t new_len, F fn)
-{
-    const size_t rl = m->row_len();
-    const size_t need = m->rows * (new_len > rl ? new_len : rl);
-    BDSP_TRY(m->v.reserve(need));
-    for (size_t r = 0; r < m->rows; ++r) BDSP_TRY(fn(m->v.data + r * rl, m->v.buf + r * new_len));
-    m->v.trade();
-    m->v.valid_len = m->rows * new_len;
-    return BDSP_OK;
 }
 
 template <typename T>
@@ -2060,17 +2047,58 @@ int mat_convolve_mimo(DevMat<T>* m, const DevVec<T>* const* h, size_t count)
     return BDSP_OK;
 }
 
+// interpolatef of every row (interp.hip): row r as op_interpolatef on it, in one launch over all rows (plus the tap
+// table's on a cache miss).  delta is left alone, as the vector call leaves it.
 template <typename T>
 int mat_interpolatef(DevMat<T>* m, int fid, T rolloff, T factor, T delay, size_t conv_len)
 {
     const size_t rl = m->row_len();
     if (rl == 0) return BDSP_OK;
     const size_t new_len = interpolatef_new_len<T>(rl, factor);
-    const bool c = m->v.complex_;
-    const T delta = m->v.delta;
-    return mat_resize_rows<T>(m, new_len, [&](const T* in, T* out) {
-        return interpolatef_dev<T>(in, out, rl, c, fid, rolloff, factor, delay, conv_len, delta, lib_stream());
-    });
+    BDSP_TRY(m->v.reserve(m->rows * (new_len > rl ? new_len : rl)));
+    BDSP_TRY(mat_interpolatef_dev<T>(m->v.data, m->v.buf, m->rows, rl, m->v.complex_, fid, rolloff, factor, delay,
+                                     (const InterpRowPrm<T>*)nullptr, conv_len, m->v.delta, lib_stream()));
+    m->v.trade();
+    m->v.valid_len = m->rows * new_len;
+    return BDSP_OK;
+}
+
+// the per-row parameter block of mat_interpolatef_delays: delay / delta (interpolation.rs:397) and the slow-pair mask of
+// that delay, conv_len clipped as the launcher clips it.  The call's only loop over rows: host arithmetic alone.
+template <typename T>
+void mat_interpf_fill_rows(InterpRowPrm<T>* prm, const T* delays, size_t rows, T delta, size_t conv_len, size_t points, int fid,
+                           T rolloff)
+{
+    if (conv_len > points / 2) conv_len = points / 2;
+    for (size_t r = 0; r < rows; ++r) {
+        const T d = delays[r] / delta;
+        prm[r].delay = d;
+        prm[r].slow_pairs = frac_slow_pairs(conv_len, (double)d, fid, (double)rolloff);
+    }
+}
+
+// interpolatef with one delay per row: the parameter block goes up by one copy, then the launches of mat_interpolatef
+// (the integer path's tap tables, one per row, by one launch into the workspace instead of the cached table)
+template <typename T>
+int mat_interpolatef_delays(DevMat<T>* m, int fid, T rolloff, T factor, const T* delays, size_t count, size_t conv_len)
+{
+    if (count != m->rows || (count > 0 && !delays)) return BDSP_ERR_ARG_LENGTH; // an argument error comes first
+    const size_t rl = m->row_len();
+    if (rl == 0) return BDSP_OK; // no rows, empty rows, poisoned (mat_code answers -1)
+    const size_t new_len = interpolatef_new_len<T>(rl, factor);
+    hipStream_t s = lib_stream();
+    std::vector<InterpRowPrm<T>> prm(m->rows);
+    mat_interpf_fill_rows<T>(prm.data(), delays, m->rows, m->v.delta, conv_len, m->row_points(), fid, rolloff);
+    WsBlock pb;
+    BDSP_TRY(pb.alloc(sizeof(InterpRowPrm<T>) * prm.size(), s));
+    // (pageable memory: the copy has left `prm` when the call returns)
+    BDSP_HIP_TRY(hipMemcpyAsync(pb.p, prm.data(), sizeof(InterpRowPrm<T>) * prm.size(), hipMemcpyHostToDevice, s));
+    BDSP_TRY(m->v.reserve(m->rows * (new_len > rl ? new_len : rl)));
+    BDSP_TRY(mat_interpolatef_dev<T>(m->v.data, m->v.buf, m->rows, rl, m->v.complex_, fid, rolloff, factor, (T)0,
+                                     pb.as<InterpRowPrm<T>>(), conv_len, m->v.delta, s));
+    m->v.trade();
+    m->v.valid_len = m->rows * new_len;
+    return BDSP_OK;
 }
 
 template <typename T>
@@ -3148,6 +3176,8 @@ BDSP_STATS(64, double, VecBuf64)
     { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_convolve_mimo<T>(a, reinterpret_cast<const DevVec<T>* const*>(impulse_responses), count)); } \
     int32_t bdsp_hip_mat_interpolatef##SFX(MB* m, int32_t impulse_response, T rolloff, T interpolation_factor, T delay, size_t conv_len) \
     { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_interpolatef<T>(a, impulse_response == 0 ? 0 : 1, rolloff, interpolation_factor, delay, conv_len)); } \
+    int32_t bdsp_hip_mat_interpolatef_delays##SFX(MB* m, int32_t impulse_response, T rolloff, T interpolation_factor, const T* delays, size_t count, size_t conv_len) \
+    { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_interpolatef_delays<T>(a, impulse_response == 0 ? 0 : 1, rolloff, interpolation_factor, delays, count, conv_len)); } \
     int32_t bdsp_hip_mat_multiply_frequency_response##SFX(MB* m, int32_t frequency_response, T rolloff, T ratio) \
     { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_multiply_frequency_response<T>(a, frequency_response == 0 ? 0 : 1, rolloff, ratio)); }
 

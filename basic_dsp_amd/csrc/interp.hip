@@ -17,6 +17,7 @@
 #include <map>
 #include <mutex>
 #include "dsp_funcs.h"
+#include "interp_core.h"
 #include "mat_interp_core.h"
 #include <vector>
 
@@ -42,46 +43,60 @@ template size_t interpolatef_new_len<float>(size_t, float);
 template size_t interpolatef_new_len<double>(size_t, double);
 
 // taps[s*ntaps + m] = f(-(L-1) + delay + m - s/factor)
-template <typename T>
-__global__ void k_interp_taps(T* __restrict__ taps, int fid, T rolloff, int conv_len, int factor, T delay)
+// ROWS: one table per row of a matrix, rows * factor * ntaps values, row r with prm[r].delay (a vector: `delay`)
+template <typename T, bool ROWS>
+__global__ void k_interp_taps(T* __restrict__ taps, int fid, T rolloff, int conv_len, int factor, T delay,
+                              const InterpRowPrm<T>* __restrict__ prm, size_t total)
 {
     // one thread per tap; each repeats the reference's own accumulation j = j + 1 up to its index, so the
     // arguments are bit-identical to the sequential loop (the serial version took 9-14 us for 100 taps)
     const int ntaps = 2 * conv_len + 1;
-    const int id = blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= factor * ntaps) return;
+    int id;
+    size_t at;
+    if constexpr (ROWS) {
+        at = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (at >= total) return;
+        const size_t row = at / (size_t)(factor * ntaps);
+        id = (int)(at - row * (size_t)(factor * ntaps));
+        delay = prm[row].delay;
+    } else {
+        id = blockIdx.x * blockDim.x + threadIdx.x;
+        if (id >= factor * ntaps) return;
+        at = (size_t)id;
+    }
     const int s = id / ntaps, m = id % ntaps;
     T offset = (T)s / (T)factor;
     T j = -((T)conv_len - (T)1) + delay;
     for (int k = 0; k < m; ++k) j = j + (T)1;
-    taps[id] = conv_time_value<T>(fid, rolloff, j - offset);
+    taps[at] = conv_time_value<T>(fid, rolloff, j - offset);
 }
 
-// The table path for the outputs outside [skip_lo, skip_hi) (all of them when the range is empty): workgroup `block` of
-// `nblocks`.  lt: LDS room for the ntaps * factor taps.
+// The table path for the outputs of ONE ROW outside [skip_lo, skip_hi) (all of them when the range is empty): workgroup
+// `block` of the row's `nblocks`.  lt: the row's ntaps * factor taps in LDS (interp_table_stage).  x, y: the row.
+template <typename T>
+__device__ __forceinline__ void interp_table_stage(const T* __restrict__ taps, T* lt, int n)
+{
+    for (int k = threadIdx.x; k < n; k += blockDim.x) lt[k] = taps[k];
+}
+
 template <typename T, bool CPLX>
-__device__ __forceinline__ void interp_table_body(const T* __restrict__ x, T* __restrict__ y, const T* __restrict__ taps, T* lt,
+__device__ __forceinline__ void interp_table_walk(const T* __restrict__ x, T* __restrict__ y, const T* lt,
                                                   long long points, long long new_points, int conv_len, int factor,
                                                   long long skip_lo, long long skip_hi, unsigned block, unsigned nblocks)
 {
     const int ntaps = 2 * conv_len + 1;
-    for (int k = threadIdx.x; k < ntaps * factor; k += blockDim.x) lt[k] = taps[k];
-    __syncthreads();
     const long long scalar_len = (long long)ntaps * factor;
     // outputs in [skip_lo, skip_hi) belong to the blocked inner kernel: walk only the two edge runs
-    const long long nskip = skip_hi > skip_lo ? skip_hi - skip_lo : 0;
+    const long long nskip = if_skip_count(skip_lo, skip_hi);
     for (long long g = (long long)block * blockDim.x + threadIdx.x; g < new_points - nskip;
          g += (long long)nblocks * blockDim.x) {
-        const long long i = (nskip && g >= skip_lo) ? g + nskip : g;
+        const long long i = if_edge_output(g, skip_lo, nskip);
         T sr = 0, si = 0;
-        const bool edge = i < scalar_len || i + scalar_len >= new_points || new_points < 2 * scalar_len;
-        if (edge) {
-            long long r = i / factor;
+        if (if_is_edge(i, scalar_len, new_points)) {
             const T* t = lt + (i % factor) * ntaps;
-            long long pos = (r - conv_len) % points;
-            if (pos < 0) pos += points;
+            long long pos = if_edge_start(i, factor, conv_len, points);
             for (int m = 0; m < ntaps; ++m) {
-                pos = pos + 1 < points ? pos + 1 : 0;
+                pos = if_wrap_next(pos, points);
                 if (CPLX) {
                     T re = x[2 * pos], im = x[2 * pos + 1];
                     sr = sr + (re * t[m] - im * (T)0);
@@ -89,9 +104,8 @@ __device__ __forceinline__ void interp_table_body(const T* __restrict__ x, T* __
                 } else sr = sr + x[pos] * t[m];
             }
         } else {
-            long long end = (i + factor - 1) / factor + conv_len;
-            int shift = (int)((factor - i % factor) % factor);
-            const T* t = lt + shift * ntaps;
+            long long end = if_inner_end(i, factor, conv_len);
+            const T* t = lt + if_inner_shift(i, factor) * ntaps;
             for (int m = ntaps - 1; m >= 0; --m) {
                 long long n = end - 1 - m;
                 if (CPLX) {
@@ -105,6 +119,16 @@ __device__ __forceinline__ void interp_table_body(const T* __restrict__ x, T* __
     }
 }
 
+template <typename T, bool CPLX>
+__device__ __forceinline__ void interp_table_body(const T* __restrict__ x, T* __restrict__ y, const T* __restrict__ taps,
+        T* lt,
+                                                  long long points, long long new_points, int conv_len, int factor,
+                                                  long long skip_lo, long long skip_hi, unsigned block, unsigned nblocks)
+{
+    interp_table_stage<T>(taps, lt, (2 * conv_len + 1) * factor);
+    __syncthreads();
+    interp_table_walk<T, CPLX>(x, y, lt, points, new_points, conv_len, factor, skip_lo, skip_hi, block, nblocks);
+}
 
 template <typename T, bool CPLX>
 __global__ __launch_bounds__(256) void k_interp_table(const T* __restrict__ x, T* __restrict__ y,
@@ -113,8 +137,40 @@ __global__ __launch_bounds__(256) void k_interp_table(const T* __restrict__ x, T
                                                        long long skip_lo, long long skip_hi)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    interp_table_body<T, CPLX>(x, y, taps, reinterpret_cast<T*>(smem_raw), points, new_points, conv_len, factor, skip_lo, skip_hi,
+    interp_table_body<T, CPLX>(x, y, taps, reinterpret_cast<T*>(smem_raw), points, new_points, conv_len, factor, skip_lo,
+            skip_hi,
                                blockIdx.x, gridDim.x);
+}
+
+// The table path over the rows of a matrix: a flat grid of rows * bpr virtual blocks, each decomposed once into
+// (row, workgroup of the row) and walked with the grid's stride.  tap_stride 0: one table for all rows (the shared delay),
+// staged once per workgroup; else row r's table is taps + r * tap_stride, restaged when the virtual block moves to
+// another row.
+template <typename T, bool CPLX>
+__global__ __launch_bounds__(256) void k_mat_interpf_table(const T* __restrict__ x, T* __restrict__ y,
+                                                            const T* __restrict__ taps, long long points,
+                                                            long long new_points, int conv_len, int factor,
+                                                            size_t rows, unsigned bpr, size_t tap_stride)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    constexpr size_t E = CPLX ? 2 : 1;
+    T* lt = reinterpret_cast<T*>(smem_raw);
+    const size_t total = rows * bpr, none = ~(size_t)0;
+    size_t staged = none; // the row whose table is in LDS (0 for the shared table)
+    for (size_t vb = blockIdx.x; vb < total; vb += gridDim.x) {
+        size_t row;
+        unsigned k;
+        if_block(vb, bpr, &row, &k);
+        const size_t want = tap_stride ? row : 0;
+        if (staged != want) {
+            if (staged != none) __syncthreads(); // every lane is done with the previous row's table
+            interp_table_stage<T>(taps + want * tap_stride, lt, (2 * conv_len + 1) * factor);
+            __syncthreads();
+            staged = want;
+        }
+        interp_table_walk<T, CPLX>(x + row * (size_t)points * E, y + row * (size_t)new_points * E, lt, points, new_points,
+                                   conv_len, factor, -1LL, -1LL, k, bpr);
+    }
 }
 
 // Inner region of the integer-factor ("simd") path, register/LDS blocked: a thread owns one input
@@ -132,26 +188,19 @@ __global__ __launch_bounds__(256) void k_interp_table(const T* __restrict__ x, T
 // Round 3: the two edge runs (the few hundred outputs next to the vector's ends, which take the table path with its
 // wrap-around) ride in the SAME launch: the workgroups past `inner_blocks` run interp_table_body on them.  As a separate
 // launch in front of this one they cost 4.8 us of config C4b's 88.
-template <typename T, bool CPLX, int FACTOR, int QB>
-__global__ __launch_bounds__(256) void k_interp_inner(const T* __restrict__ x, T* __restrict__ y,
-                                                      const T* __restrict__ taps, long long q_lo,
-                                                      long long q_hi, int conv_len, long long points,
-                                                      long long new_points, unsigned inner_blocks, int stream_out)
+// One tile: positions [q0, min(q0 + TILE, q_hi)) of the row x -> y.  ROWS: y may start on any scalar (a matrix row).
+template <typename T, bool CPLX, int FACTOR, int QB, bool ROWS>
+__device__ __forceinline__ void interp_inner_tile(const T* __restrict__ x, T* __restrict__ y, const T* __restrict__ taps,
+                                                  unsigned char* smem_raw, long long q0, long long q_hi, int conv_len,
+                                                  long long points, int stream_out)
 {
     constexpr int E = CPLX ? 2 : 1;
     constexpr int TILE = 256 * QB;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    if (blockIdx.x >= inner_blocks) {
-        interp_table_body<T, CPLX>(x, y, taps, reinterpret_cast<T*>(smem_raw), points, new_points, conv_len, FACTOR,
-                                   q_lo * FACTOR, q_hi * FACTOR, blockIdx.x - inner_blocks, gridDim.x - inner_blocks);
-        return;
-    }
     const int ntaps = 2 * conv_len + 1;
     T* lt = reinterpret_cast<T*>(smem_raw);                 // [ntaps + 1][FACTOR]
     T* lx = lt + ((FACTOR * (ntaps + 1) + 3) & ~3);         // [TILE + 2L + 2][E]
     T* lo = lx + ((TILE + 2 * conv_len + 2) * E + 3 & ~3);  // [TILE * FACTOR][E] output staging
     const int t = threadIdx.x;
-    const long long q0 = q_lo + (long long)blockIdx.x * TILE;
     // tap table re-laid out per step j of the walk below: lt[j*FACTOR + s] is the tap that x[q-L-1+j] carries
     // into output s (0 where it carries none), so one wide LDS read per step fetches all FACTOR taps:
     //   s = 0: m = 2L - j (j <= 2L)          s > 0: m = 2L + 1 - j (j >= 1), tap vector f - s
@@ -163,8 +212,8 @@ __global__ __launch_bounds__(256) void k_interp_inner(const T* __restrict__ x, T
         lt[k] = w;
     }
     // x[q0 - L - 1 .. q0 + TILE - 1 + L]  (always in range below: the inner region starts (2L+1) positions in)
-    const int span = TILE + 2 * conv_len + 2;
-    const long long xbase = q0 - conv_len - 1;
+    const int span = if_tile_span(TILE, conv_len);
+    const long long xbase = if_tile_xbase(q0, conv_len);
     for (int k = t; k < span * E; k += 256) {
         long long g = xbase * E + k;
         lx[k] = g < points * E ? x[g] : (T)0; // the last workgroup's tile may overhang the vector
@@ -224,8 +273,7 @@ __global__ __launch_bounds__(256) void k_interp_inner(const T* __restrict__ x, T
         }
     }
     }
-    long long nq = q_hi - q0;
-    if (nq > TILE) nq = TILE;
+    const long long nq = if_tile_nq(q0, q_hi, TILE);
     const long long out0 = q0 * FACTOR * E, nout = nq * FACTOR * E;
     constexpr int VN = 16 / sizeof(T); // scalars per 16-byte packet
     constexpr int PER_THREAD = QB * FACTOR * E; // scalars a thread hands over
@@ -235,13 +283,12 @@ __global__ __launch_bounds__(256) void k_interp_inner(const T* __restrict__ x, T
         // ds_write_b128 of a thread start PP*16 bytes after its neighbour's: the hardware serves such a store in groups
         // of 8 lanes over 32 dword banks, so with PP = 4 lanes 0/2/4/6 meet on one bank -- four-way conflicts, the 20 %
         // LDS conflict cycles the round-2 PMC showed for config C4b.  The packets of thread t are therefore ROTATED
-        // within its own PP slots by (t / (8 / PP)) mod PP (PP < 8) or t mod PP: eight consecutive lanes then cover
+        // within its own PP slots by (t / (8 / PP)) mod PP (PP < 8) or t mod PP (if_lo_slot, interp_core.h): eight consecutive lanes then cover
         // eight different 16-byte bank groups, and the reader -- which takes packet k = PP*t' + part from slot
         // PP*t' + ((part + rot(t')) mod PP) -- still sees each aligned run of PP slots exactly once per PP lanes.
         constexpr int PP = PER_THREAD / VN;
         typedef T vecT __attribute__((ext_vector_type(VN)));
         vecT* lov = reinterpret_cast<vecT*>(lo);
-        auto rot = [](int q) { return PP >= 8 ? (q & (PP - 1)) : (PP > 1 ? ((q / (8 / (PP > 1 ? PP : 1))) & (PP - 1)) : 0); };
         static_assert((PP & (PP - 1)) == 0 || PP == 3 || PP == 6 || PP == 12, "rotation below handles any PP");
         T flat[PER_THREAD];
 #pragma unroll
@@ -251,28 +298,39 @@ __global__ __launch_bounds__(256) void k_interp_inner(const T* __restrict__ x, T
                 flat[(k * FACTOR + s) * E] = ar[k][s];
                 if (CPLX) flat[(k * FACTOR + s) * E + 1] = ai[k][s];
             }
-        constexpr bool POW2 = (PP & (PP - 1)) == 0;
-        const int r = POW2 ? rot(t) : 0;
 #pragma unroll
         for (int part = 0; part < PP; ++part) {
             vecT pk;
 #pragma unroll
             for (int e = 0; e < VN; ++e) pk[e] = flat[part * VN + e];
-            lov[PP * t + (POW2 ? ((part + r) & (PP - 1)) : part)] = pk;
+            lov[if_lo_slot(t, part, PP)] = pk;
         }
         __syncthreads();
+        if constexpr (ROWS) {
+            // A matrix row starts on any scalar (real rows of odd length; every second output row when new_len is
+            // 2 mod 4): packets go out only where this tile's first output is 16-byte aligned -- the whole row is then,
+            // out0 being a multiple of VN -- and scalar by scalar from the same rotated slots otherwise.
+            if ((reinterpret_cast<size_t>(y + out0) & 15) != 0) {
+                for (long long k = t; k < nout; k += 256) {
+                    const int pk = (int)(k / VN), e = (int)(k % VN);
+                    const int q = pk / PP, part = pk % PP;
+                    y[out0 + k] = lo[if_lo_slot(q, part, PP) * VN + e];
+                }
+                return;
+            }
+        }
         vecT* yv = reinterpret_cast<vecT*>(y + out0);
         // A result too large for the 256 MB Infinity Cache to hold until its reader comes is STREAMED (non-temporal
         // stores): config C4b's 256 MB ran 82 -> 69 us that way; a result that fits (128 MB: 46 -> 48 us) is not.
         if (stream_out) {
             for (long long k = t; k < nout / VN; k += 256) {
                 const int q = (int)(k / PP), part = (int)(k % PP);
-                __builtin_nontemporal_store(lov[PP * q + (POW2 ? ((part + rot(q)) & (PP - 1)) : part)], &yv[k]);
+                __builtin_nontemporal_store(lov[if_lo_slot(q, part, PP)], &yv[k]);
             }
         } else {
             for (long long k = t; k < nout / VN; k += 256) {
                 const int q = (int)(k / PP), part = (int)(k % PP);
-                yv[k] = lov[PP * q + (POW2 ? ((part + rot(q)) & (PP - 1)) : part)];
+                yv[k] = lov[if_lo_slot(q, part, PP)];
             }
         }
     } else {
@@ -288,19 +346,125 @@ __global__ __launch_bounds__(256) void k_interp_inner(const T* __restrict__ x, T
     }
 }
 
-template <typename T, bool CPLX>
-__global__ __launch_bounds__(256) void k_interp_scalar(const T* __restrict__ x, T* __restrict__ y,
-                                                        long long points, long long new_points,
-                                                        int conv_len, T factor, T delay, int fid, T rolloff)
+template <typename T, bool CPLX, int FACTOR, int QB>
+__global__ __launch_bounds__(256) void k_interp_inner(const T* __restrict__ x, T* __restrict__ y,
+                                                      const T* __restrict__ taps, long long q_lo,
+                                                      long long q_hi, int conv_len, long long points,
+                                                      long long new_points, unsigned inner_blocks, int stream_out)
+{
+    constexpr int TILE = 256 * QB;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    if (blockIdx.x >= inner_blocks) {
+        interp_table_body<T, CPLX>(x, y, taps, reinterpret_cast<T*>(smem_raw), points, new_points, conv_len, FACTOR,
+                                   q_lo * FACTOR, q_hi * FACTOR, blockIdx.x - inner_blocks, gridDim.x - inner_blocks);
+        return;
+    }
+    interp_inner_tile<T, CPLX, FACTOR, QB, false>(x, y, taps, smem_raw, q_lo + (long long)blockIdx.x * TILE, q_hi, conv_len,
+                                                  points, stream_out);
+}
+
+// The same over the rows of a matrix: a flat grid of rows * (inner_blocks + edge_blocks) virtual blocks, each decomposed
+// once into (row, tile or edge workgroup of the row) and walked with the grid's stride.  Every virtual block stages its
+// own LDS image (the tile's re-laid-out table and the edge walk's plain one share the room), so a workgroup that moves to
+// another row never reads a table it did not stage for that row.  tap_stride 0: one table for all rows.
+template <typename T, bool CPLX, int FACTOR, int QB>
+__global__ __launch_bounds__(256) void k_mat_interpf_inner(const T* __restrict__ x, T* __restrict__ y,
+                                                           const T* __restrict__ taps, long long q_lo,
+                                                           long long q_hi, int conv_len, long long points,
+                                                           long long new_points, unsigned inner_blocks,
+                                                           unsigned edge_blocks, size_t rows, size_t tap_stride,
+                                                           int stream_out)
+{
+    constexpr int TILE = 256 * QB;
+    constexpr size_t E = CPLX ? 2 : 1;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const unsigned per_row = inner_blocks + edge_blocks;
+    const size_t total = rows * per_row;
+    for (size_t vb = blockIdx.x; vb < total; vb += gridDim.x) {
+        size_t row;
+        unsigned k;
+        if_block(vb, per_row, &row, &k);
+        if (vb != blockIdx.x) __syncthreads(); // every lane is done with the previous virtual block's LDS image
+        const T* xr = x + row * (size_t)points * E;
+        T* yr = y + row * (size_t)new_points * E;
+        const T* tr = taps + row * tap_stride;
+        if (k < inner_blocks)
+            interp_inner_tile<T, CPLX, FACTOR, QB, true>(xr, yr, tr, smem_raw, q_lo + (long long)k * TILE, q_hi, conv_len,
+                                                         points, stream_out);
+        else
+            interp_table_body<T, CPLX>(xr, yr, tr, reinterpret_cast<T*>(smem_raw), points, new_points, conv_len, FACTOR,
+                                       q_lo * FACTOR, q_hi * FACTOR, k - inner_blocks, edge_blocks);
+    }
+}
+
+// The walk of the scalar paths over a lane's outputs.  A vector: i = first, first + stride, ... below new_points.  The rows
+// of a matrix (ROWS): the lane owns flat output g of rows * new_points, (row, i) by one division (if_pos), and advances
+// by the grid's stride with two adds and a compare (if_advance); x, y, the delay and the slow-pair mask are the row's
+// (prm: one block per row, or null for a delay all rows share).
+template <typename T, bool CPLX, bool ROWS, typename IDX>
+struct InterpWalk {
+    const T* x;
+    T* y;
+    long long i;
+    T delay;
+    unsigned long long slow_pairs;
+    const T* xb;
+    T* yb;
+    const InterpRowPrm<T>* prm;
+    IfPos<IDX> at, step;
+    IDX rows, width;
+    size_t in_row, out_row;
+    long long stride;
+    __device__ __forceinline__ InterpWalk(const T* x_, T* y_, long long points, long long new_points, T delay_,
+                                          unsigned long long slow_, size_t rows_, const InterpRowPrm<T>* prm_,
+                                          long long first, long long stride_)
+    {
+        x = x_; y = y_; delay = delay_; slow_pairs = slow_;
+        stride = stride_;
+        i = first;
+        if constexpr (ROWS) {
+            xb = x_; yb = y_; prm = prm_;
+            rows = (IDX)rows_; width = (IDX)new_points;
+            in_row = (size_t)points * (CPLX ? 2 : 1); out_row = (size_t)new_points * (CPLX ? 2 : 1);
+            at = if_pos<IDX>((IDX)first, width);
+            step = if_pos<IDX>((IDX)stride, width);
+            load();
+        }
+    }
+    __device__ __forceinline__ void load()
+    {
+        if (at.row < rows) {
+            x = xb + (size_t)at.row * in_row;
+            y = yb + (size_t)at.row * out_row;
+            i = (long long)at.col;
+            if (prm) { delay = prm[at.row].delay; slow_pairs = prm[at.row].slow_pairs; }
+        }
+    }
+    __device__ __forceinline__ bool valid(long long new_points) const
+    {
+        if constexpr (ROWS) return at.row < rows;
+        else return i < new_points;
+    }
+    __device__ __forceinline__ void next()
+    {
+        if constexpr (ROWS) { if_advance<IDX>(&at, step, width); load(); }
+        else i += stride;
+    }
+};
+
+template <typename T, bool CPLX, bool ROWS, typename IDX>
+__device__ __forceinline__ void interp_scalar_body(const T* __restrict__ x_, T* __restrict__ y_, long long points,
+        long long new_points, int conv_len, T factor, T delay_, int fid, T rolloff, size_t rows,
+        const InterpRowPrm<T>* __restrict__ prm, long long first,
+        long long stride)
 {
     double rot_s = 0.0, rot_c = 1.0;
     if (fid != 0) sincospi((double)rolloff, &rot_s, &rot_c);
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < new_points;
-         i += (long long)gridDim.x * blockDim.x) {
+    // one output: i of the row x -> y.  The vector call keeps its own plain loop, so the row walk costs it nothing.
+    auto output = [&](const T* x, T* y, const long long i, const T delay) {
         T center = (T)i / factor;
         T rounded = dev_floor<T>(center);
-        long long pos = ((long long)rounded - conv_len - 1) % points;
-        if (pos < 0) pos += points;
+        long long pos = if_scalar_start((long long)rounded, conv_len, points);
         T j = -(T)conv_len - (center - rounded) + delay;
         T sr = 0, si = 0;
         // The tap arguments of one output are j, j+1, j+2, ...: sin(pi (j+k)) = (-1)^k sin(pi j), and the raised
@@ -343,7 +507,33 @@ __global__ __launch_bounds__(256) void k_interp_scalar(const T* __restrict__ x, 
         }
         if (CPLX) { y[2 * i] = sr; y[2 * i + 1] = si; }
         else y[i] = sr;
+    };
+    if constexpr (ROWS) {
+        for (InterpWalk<T, CPLX, ROWS, IDX> wk(x_, y_, points, new_points, delay_, 0ull, rows, prm, first, stride); wk.valid(new_points); wk.next())
+            output(wk.x, wk.y, wk.i, wk.delay);
+    } else {
+        for (long long i = first; i < new_points; i += stride)
+            output(x_, y_, i, delay_);
     }
+}
+
+template <typename T, bool CPLX>
+__global__ __launch_bounds__(256) void k_interp_scalar(const T* __restrict__ x, T* __restrict__ y, long long points,
+        long long new_points, int conv_len, T factor, T delay, int fid, T rolloff)
+{
+    interp_scalar_body<T, CPLX, false, long long>(x, y, points, new_points, conv_len, factor, delay, fid, rolloff,
+            (size_t)1, (const InterpRowPrm<T>*)nullptr,
+        (long long)blockIdx.x * blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x);
+}
+
+// the rows of a matrix, IDX wide indices for the flat walk
+template <typename T, bool CPLX, typename IDX>
+__global__ __launch_bounds__(256) void k_mat_interpf_scalar(const T* __restrict__ x, T* __restrict__ y, long long points,
+        long long new_points, int conv_len, T factor, T delay, int fid, T rolloff, size_t rows,
+        const InterpRowPrm<T>* __restrict__ prm)
+{
+    interp_scalar_body<T, CPLX, true, IDX>(x, y, points, new_points, conv_len, factor, delay, fid, rolloff, rows, prm,
+        (long long)blockIdx.x * blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x);
 }
 
 // Round 4: the scalar path again, two to three times faster (fractional factors are what interpolatef is FOR: 44.1 -> 48 kHz
@@ -360,12 +550,12 @@ template <typename T> __device__ __forceinline__ T quot(T a, T b) { return a / b
 // instruction); the weights move by an ulp or two, three orders below the 1e-6 the path is held to
 template <> __device__ __forceinline__ float quot<float>(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
 
-template <typename T, bool CPLX>
-__global__ __launch_bounds__(256) void k_interp_scalar_v2(const T* __restrict__ x, T* __restrict__ y,
-                                                           long long points_, long long new_points,
-                                                           int conv_len, T factor, T delay, int fid, T rolloff)
+template <typename T, bool CPLX, bool ROWS, typename IDX>
+__device__ __forceinline__ void interp_scalar_v2_body(unsigned char* smem_raw, const T* __restrict__ x_,
+        T* __restrict__ y_, long long points_, long long new_points, int conv_len, T factor, T delay_, int fid, T rolloff,
+        size_t rows, const InterpRowPrm<T>* __restrict__ prm, long long first,
+        long long stride)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T* tabc = reinterpret_cast<T*>(smem_raw);
     const int ntaps = 2 * conv_len + 1;
     T* tabs = tabc + ntaps;
@@ -379,8 +569,8 @@ __global__ __launch_bounds__(256) void k_interp_scalar_v2(const T* __restrict__ 
         __syncthreads();
     }
     typedef T vec2 __attribute__((ext_vector_type(2)));
-    typedef int IDX; // 32-bit positions in the tap loop: the launcher sends vectors of 2^31 points or more to k_interp_scalar
-    const IDX points = (IDX)points_;
+    typedef int PIDX; // 32-bit positions in the tap loop: the launcher sends vectors of 2^31 points or more to k_interp_scalar
+    const PIDX points = (PIDX)points_;
     const T one = (T)1, two = (T)2, pi = (T)3.14159265358979323846;
     // the value at the raised cosine's second singularity, |j| = 1 / (2 beta) (conv_types.rs:406-424)
     T wsing = one;
@@ -390,13 +580,12 @@ __global__ __launch_bounds__(256) void k_interp_scalar_v2(const T* __restrict__ 
         wsing = dev_sin(arg) / arg * pi / (two * two);
     }
     const T tworo = two * rolloff;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < new_points;
-         i += (long long)gridDim.x * blockDim.x) {
+    // one output: i of the row x -> y.  The vector call keeps its own plain loop, so the row walk costs it nothing.
+    auto output = [&](const T* x, T* y, const long long i, const T delay) {
         const T center = (T)i / factor;
         const T rounded = dev_floor<T>(center);
-        long long p0 = ((long long)rounded - conv_len - 1) % points_;
-        if (p0 < 0) p0 += points_;
-        IDX pos = (IDX)p0;
+        const long long p0 = if_scalar_start((long long)rounded, conv_len, points_);
+        PIDX pos = (PIDX)p0;
         T j = -(T)conv_len - (center - rounded) + delay;
         // (sinpi / sincospi reduce their argument exactly, so T's own versions are as good as the double ones here; the
         // product beta * j rounds like the reference's own pi * x * beta does)
@@ -442,7 +631,36 @@ __global__ __launch_bounds__(256) void k_interp_scalar_v2(const T* __restrict__ 
         }
         if (CPLX) reinterpret_cast<vec2*>(y)[i] = acc;
         else y[i] = sr;
+    };
+    if constexpr (ROWS) {
+        for (InterpWalk<T, CPLX, ROWS, IDX> wk(x_, y_, points_, new_points, delay_, 0ull, rows, prm, first, stride); wk.valid(new_points); wk.next())
+            output(wk.x, wk.y, wk.i, wk.delay);
+    } else {
+        for (long long i = first; i < new_points; i += stride)
+            output(x_, y_, i, delay_);
     }
+}
+
+template <typename T, bool CPLX>
+__global__ __launch_bounds__(256) void k_interp_scalar_v2(const T* __restrict__ x, T* __restrict__ y, long long points,
+        long long new_points, int conv_len, T factor, T delay, int fid, T rolloff)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    interp_scalar_v2_body<T, CPLX, false, long long>(smem_raw, x, y, points, new_points, conv_len, factor, delay, fid,
+            rolloff, (size_t)1, (const InterpRowPrm<T>*)nullptr,
+        (long long)blockIdx.x * blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x);
+}
+
+// the rows of a matrix, IDX wide indices for the flat walk
+template <typename T, bool CPLX, typename IDX>
+__global__ __launch_bounds__(256) void k_mat_interpf_scalar_v2(const T* __restrict__ x, T* __restrict__ y, long long points,
+        long long new_points, int conv_len, T factor, T delay, int fid, T rolloff, size_t rows,
+        const InterpRowPrm<T>* __restrict__ prm)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    interp_scalar_v2_body<T, CPLX, true, IDX>(smem_raw, x, y, points, new_points, conv_len, factor, delay, fid, rolloff,
+            rows, prm,
+        (long long)blockIdx.x * blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x);
 }
 
 // Round 6: the fractional path with TWO TAPS PER PACKED INSTRUCTION (f32: v_pk_mul_f32 / v_pk_add_f32 on (tap k, tap k+1); f64
@@ -493,14 +711,13 @@ __device__ __forceinline__ T frac_tap_weight(const FracCtx<T>& c, T j, T sjk, in
     return j == (T)0 ? one : w;
 }
 
-template <typename T, bool CPLX>
-__global__ __launch_bounds__(256) void k_interp_frac_pk(const T* __restrict__ x, T* __restrict__ y,
-                                                         long long points_, long long new_points, int conv_len,
-                                                         T factor, T delay, int fid, T rolloff,
-                                                         unsigned long long slow_pairs)
+template <typename T, bool CPLX, bool ROWS, typename IDX>
+__device__ __forceinline__ void interp_frac_pk_body(unsigned char* smem_raw, const T* __restrict__ x_, T* __restrict__ y_,
+        long long points_, long long new_points, int conv_len, T factor, T delay_, int fid, T rolloff,
+        unsigned long long slow_pairs_, size_t rows, const InterpRowPrm<T>* __restrict__ prm, long long first,
+        long long stride)
 {
     typedef T v2f __attribute__((ext_vector_type(2))); // (f64: the same structure on pairs of scalar operations)
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int ntaps = 2 * conv_len + 1;
     const int npairs = ntaps >> 1; // ntaps is odd: the last tap goes alone
     T* tabc = reinterpret_cast<T*>(smem_raw);
@@ -526,11 +743,11 @@ __global__ __launch_bounds__(256) void k_interp_frac_pk(const T* __restrict__ x,
     }
     c.tworo = two * rolloff;
     const v2f pi2 = v2f{pi, pi}, tworo2 = v2f{c.tworo, c.tworo}, one2 = v2f{one, one};
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < new_points; i += (long long)gridDim.x * blockDim.x) {
+    // one output: i of the row x -> y.  The vector call keeps its own plain loop, so the row walk costs it nothing.
+    auto output = [&](const T* x, T* y, const long long i, const T delay, const unsigned long long slow_pairs) {
         const T center = (T)i / factor;
         const T rounded = dev_floor<T>(center);
-        long long p0 = ((long long)rounded - conv_len - 1) % points_;
-        if (p0 < 0) p0 += points_;
+        const long long p0 = if_scalar_start((long long)rounded, conv_len, points_);
         const T j0 = -(T)conv_len - (center - rounded) + delay;
         T sj, cdummy;
         dev_sincospi<T>(j0, &sj, &cdummy);
@@ -558,7 +775,7 @@ __global__ __launch_bounds__(256) void k_interp_frac_pk(const T* __restrict__ x,
         };
         v2f acc = v2f{(T)0, (T)0};
         T sr = (T)0;
-        const bool wraps = p0 + ntaps >= points_;
+        const bool wraps = if_frac_wraps(p0, ntaps, points_); // of this lane's ROW
         if (__builtin_amdgcn_ballot_w64(wraps) != 0ull) {
             faithful(acc, sr);
         } else {
@@ -609,14 +826,43 @@ __global__ __launch_bounds__(256) void k_interp_frac_pk(const T* __restrict__ x,
         }
         if (CPLX) reinterpret_cast<v2f*>(y)[i] = acc;
         else y[i] = sr;
+    };
+    if constexpr (ROWS) {
+        for (InterpWalk<T, CPLX, ROWS, IDX> wk(x_, y_, points_, new_points, delay_, slow_pairs_, rows, prm, first, stride); wk.valid(new_points); wk.next())
+            output(wk.x, wk.y, wk.i, wk.delay, wk.slow_pairs);
+    } else {
+        for (long long i = first; i < new_points; i += stride)
+            output(x_, y_, i, delay_, slow_pairs_);
     }
+}
+
+template <typename T, bool CPLX>
+__global__ __launch_bounds__(256) void k_interp_frac_pk(const T* __restrict__ x, T* __restrict__ y, long long points,
+        long long new_points, int conv_len, T factor, T delay, int fid, T rolloff, unsigned long long slow_pairs)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    interp_frac_pk_body<T, CPLX, false, long long>(smem_raw, x, y, points, new_points, conv_len, factor, delay, fid,
+            rolloff, slow_pairs, (size_t)1, (const InterpRowPrm<T>*)nullptr,
+        (long long)blockIdx.x * blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x);
+}
+
+// the rows of a matrix, IDX wide indices for the flat walk
+template <typename T, bool CPLX, typename IDX>
+__global__ __launch_bounds__(256) void k_mat_interpf_frac_pk(const T* __restrict__ x, T* __restrict__ y, long long points,
+        long long new_points, int conv_len, T factor, T delay, int fid, T rolloff, unsigned long long slow_pairs, size_t rows,
+        const InterpRowPrm<T>* __restrict__ prm)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    interp_frac_pk_body<T, CPLX, true, IDX>(smem_raw, x, y, points, new_points, conv_len, factor, delay, fid, rolloff,
+            slow_pairs, rows, prm,
+        (long long)blockIdx.x * blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x);
 }
 
 // the pairs of taps (2p, 2p+1) that can hold a special tap, for every output of a launch: tap k has
 // j = k - L - frac + delay with frac in [0, 1).  Special: j == 0 (weight 1), and for the raised cosine |1 - |2 beta j|| < 0.25
 // (the cancellation-free form and, inside it, the singularity |j| == 1 / (2 beta)).  Intervals widened by a margin far above
 // the rounding of the accumulated j.  All ones = every pair takes the per-tap code (odd parameters).
-static unsigned long long frac_slow_pairs(size_t conv_len, double delay, int fid, double rolloff)
+unsigned long long frac_slow_pairs(size_t conv_len, double delay, int fid, double rolloff)
 {
     const long long ntaps = 2 * (long long)conv_len + 1;
     if (ntaps > 128 || !(delay == delay) || delay > 1e6 || delay < -1e6) return ~0ull;
@@ -712,7 +958,8 @@ static int interp_tap_table(int fid, T rolloff, int conv_len, int f, T delay, hi
     const bool cache = g_tap_cache.size() < 32 && query_ok && cap == hipStreamCaptureStatusNone;
     if (cache) BDSP_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dst), bytes));
     else { BDSP_TRY(fallback->alloc(bytes, s)); dst = fallback->as<T>(); }
-    hipLaunchKernelGGL((k_interp_taps<T>), dim3((f * ntaps + 63) / 64), dim3(64), 0, s, dst, fid, rolloff, conv_len, f, delay);
+    hipLaunchKernelGGL((k_interp_taps<T, false>), dim3((f * ntaps + 63) / 64), dim3(64), 0, s, dst, fid, rolloff, conv_len, f, delay,
+                       (const InterpRowPrm<T>*)nullptr, (size_t)0);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && cache) e = hipStreamSynchronize(s);
     if (e != hipSuccess) {
@@ -724,29 +971,87 @@ static int interp_tap_table(int fid, T rolloff, int conv_len, int f, T delay, hi
     return BDSP_OK;
 }
 
+// Which of the reference's two paths a row of `len` scalars takes and which kernel serves it -- ONE decision for the vector
+// call and for the rows of a matrix, so a row of a matrix runs the kernel body the vector call would run on it.
+enum InterpPath { IF_TABLE, IF_BLOCKED, IF_FRAC_PK, IF_SCALAR_V2, IF_SCALAR };
+struct InterpPlan {
+    size_t points, conv_len, new_len, new_points;
+    bool simd;    // the reference's integer-factor path (interpolation.rs:411-414)
+    int f, ntaps; // simd: the integer factor; taps per output
+    int qb;       // blocked: input positions per thread
+    IfGeom g;     // simd: tiles and edge workgroups of one row
+    InterpPath path;
+};
+
+// edge_cap: most workgroups a row's table path may use
 template <typename T>
-int interpolatef_dev(const T* in, T* out, size_t len, bool is_complex, int fid, T rolloff, T factor,
-                     T delay, size_t conv_len, T delta, hipStream_t s, T (*host_fn)(const void*, T),
-                     const void* host_fn_data)
+static InterpPlan interp_plan(size_t len, bool is_complex, T factor, size_t conv_len, size_t edge_cap)
 {
+    InterpPlan p{};
     const size_t elem = is_complex ? 2 : 1;
-    const size_t points = len / elem;
-    if (points == 0) return BDSP_OK;
-    delay = delay / delta;                                    // interpolation.rs:397
-    if (conv_len > points / 2) conv_len = points / 2;         // :399-404
-    const size_t new_len = interpolatef_new_len<T>(len, factor);
-    const size_t new_points = new_len / elem;
-    if (new_points == 0) return BDSP_OK;
+    p.points = len / elem;
+    if (conv_len > p.points / 2) conv_len = p.points / 2;     // interpolation.rs:399-404
+    p.conv_len = conv_len;
+    p.new_len = interpolatef_new_len<T>(len, factor);
+    p.new_points = p.new_len / elem;
+    p.ntaps = 2 * (int)conv_len + 1;
     T rf = sizeof(T) == 4 ? (T)roundf((float)factor) : (T)round((double)factor);
     T dif = rf - factor;
     if (dif < 0) dif = -dif;
-    const bool simd = conv_len <= 202 && new_len >= 2000 && dif < (T)1e-6; // :411-414
-    size_t blocks = (new_points + 255) / 256;
+    p.simd = conv_len <= 202 && p.new_len >= 2000 && dif < (T)1e-6; // :411-414
+    if (p.simd) {
+        p.f = (int)rf;
+        // positions per thread: as many as keep the output staging buffer at 32 KB
+        // *measured* (round 3, tools/c4b_bench.py, 4M -> 16M): real f64 with 1 / 2 / 3 / 4 positions per thread 45.4 / 35.9 /
+        // 34.9 / 37.4 us; complex f32 with 1 / 2 / 4: 40.6 / 40.0 / 45.5; complex f64 stays at 1 (round 2: 2 halves the
+        // occupancy through its 32 KB staging buffer)
+        p.qb = is_complex ? (sizeof(T) == 4 ? 2 : 1) : (sizeof(T) == 4 ? 4 : 2);
+        const int f = p.f;
+        // edges (and everything, for factors without a blocked instantiation) by the table path; the inner region by
+        // the blocked kernel where one exists -- one launch then, the edge runs taken by its last workgroups
+        p.g = if_geom((long long)p.points, (long long)p.new_points, (int)conv_len, f, 256u * (unsigned)p.qb,
+                      f == 2 || f == 3 || f == 4 || f == 8, (unsigned)edge_cap);
+        p.path = p.g.blocked ? IF_BLOCKED : IF_TABLE;
+    } else {
+        const size_t tab_bytes = (size_t)2 * (2 * conv_len + 1) * sizeof(T);
+        // k_interp_scalar_v2 wherever the cos / sin table of the roll-off lattice fits 48 KB of LDS (every practical conv_len:
+        // up to 3071 taps a side in f32, 1535 in f64) and positions fit 32 bits; otherwise the first-generation kernel
+        // (tests/test_gpu_parity.py::test_interpolatef_fractional_factor_kernel_singularities_and_fallback runs both)
+        // at most 127 taps (the slow-pair mask is one 64-bit word; above: k_interp_scalar_v2)
+        if (2 * conv_len + 1 <= 127 && p.points < ((size_t)1 << 31)) p.path = IF_FRAC_PK;
+        else if (tab_bytes <= 48 * 1024 && p.points < ((size_t)1 << 31)) p.path = IF_SCALAR_V2;
+        else p.path = IF_SCALAR;
+    }
+    return p;
+}
+
+// LDS of the blocked kernel: the re-laid-out table, the x window and the output staging (never below the table path's)
+template <typename T>
+static size_t interp_inner_lds(const InterpPlan& p, bool is_complex)
+{
+    const size_t e = is_complex ? 2 : 1, tile = p.g.tile, f = (size_t)p.f;
+    size_t lds2 = sizeof(T) * (((f * (p.ntaps + 1) + 3) & ~(size_t)3) + (((tile + 2 * p.conv_len + 2) * e + 3) & ~(size_t)3) + tile * f * e);
+    const size_t lds = sizeof(T) * (size_t)p.ntaps * f;
+    return lds2 < lds ? lds : lds2;
+}
+
+template <typename T>
+int interpolatef_dev(const T* in, T* out, size_t len, bool is_complex, int fid, T rolloff, T factor,
+                     T delay, size_t conv_len_arg, T delta, hipStream_t s, T (*host_fn)(const void*, T),
+                     const void* host_fn_data)
+{
+    const size_t elem = is_complex ? 2 : 1;
+    if (len / elem == 0) return BDSP_OK;
+    delay = delay / delta;                                    // interpolation.rs:397
+    const size_t new_points_all = interpolatef_new_len<T>(len, factor) / elem;
+    if (new_points_all == 0) return BDSP_OK;
+    size_t blocks = (new_points_all + 255) / 256;
     size_t cap = (size_t)num_cus() * 8;
     if (blocks > cap) blocks = cap;
-    if (simd) {
-        int f = (int)rf;
-        int ntaps = 2 * (int)conv_len + 1;
+    const InterpPlan plan = interp_plan<T>(len, is_complex, factor, conv_len_arg, blocks);
+    const size_t points = plan.points, conv_len = plan.conv_len, new_len = plan.new_len, new_points = plan.new_points;
+    if (plan.simd) {
+        const int f = plan.f, ntaps = plan.ntaps;
         WsBlock tb;
         const T* taps_dev = nullptr;
         if (host_fn) { // the callback variant: the same table, sampled on the host
@@ -765,14 +1070,7 @@ int interpolatef_dev(const T* in, T* out, size_t len, bool is_complex, int fid, 
         }
         size_t lds = sizeof(T) * (size_t)ntaps * f;
         if (lds > 60 * 1024) { set_last_error("interpolatef: tap table exceeds LDS"); return BDSP_ERR_UNSUPPORTED; }
-        // edges (and everything, for factors without a blocked instantiation) by the table path; the inner region by
-        // the blocked kernel where one exists -- one launch then, the edge runs taken by its last workgroups
-        const long long scalar_len = (long long)ntaps * f;
-        long long q_lo = (scalar_len + f - 1) / f;                   // first q with f*q >= scalar_len
-        long long q_hi = ((long long)new_points - scalar_len) / f;   // f*q + f - 1 < new_points - scalar_len
-        const bool blocked = (f == 2 || f == 3 || f == 4 || f == 8) && q_hi > q_lo &&
-                             (long long)new_points >= 2 * scalar_len;
-        if (!blocked) {
+        if (plan.path == IF_TABLE) {
             if (is_complex)
                 hipLaunchKernelGGL((k_interp_table<T, true>), dim3((unsigned)blocks), dim3(256), lds, s, in, out,
                                    taps_dev, (long long)points, (long long)new_points, (int)conv_len, f, -1LL, -1LL);
@@ -780,23 +1078,13 @@ int interpolatef_dev(const T* in, T* out, size_t len, bool is_complex, int fid, 
                 hipLaunchKernelGGL((k_interp_table<T, false>), dim3((unsigned)blocks), dim3(256), lds, s, in, out,
                                    taps_dev, (long long)points, (long long)new_points, (int)conv_len, f, -1LL, -1LL);
         } else {
-            const size_t edge_outputs = new_points - (size_t)((q_hi - q_lo) * f);
-            size_t eblocks = (edge_outputs + 255) / 256;
-            if (eblocks > blocks) eblocks = blocks;
-            if (eblocks < 1) eblocks = 1;
-            const int e = is_complex ? 2 : 1;
-            // positions per thread: as many as keep the output staging buffer at 32 KB
-            // *measured* (round 3, tools/c4b_bench.py, 4M -> 16M): real f64 with 1 / 2 / 3 / 4 positions per thread 45.4 / 35.9 /
-            // 34.9 / 37.4 us; complex f32 with 1 / 2 / 4: 40.6 / 40.0 / 45.5; complex f64 stays at 1 (round 2: 2 halves the
-            // occupancy through its 32 KB staging buffer)
+            const long long q_lo = plan.g.q_lo, q_hi = plan.g.q_hi;
+            const size_t eblocks = plan.g.edge_blocks;
             constexpr int QB = sizeof(T) == 4 ? 2 : 1;   // complex
             constexpr int QBR = sizeof(T) == 4 ? 4 : 2;  // real
-            const int qb = is_complex ? QB : QBR;
-            const size_t tile = 256 * (size_t)qb;
-            size_t lds2 = sizeof(T) * ((((size_t)f * (ntaps + 1) + 3) & ~(size_t)3) + (((tile + 2 * conv_len + 2) * e + 3) & ~(size_t)3) + tile * (size_t)f * e);
-            if (lds2 < lds) lds2 = lds;
-            const unsigned g = (unsigned)((q_hi - q_lo + (long long)tile - 1) / (long long)tile);
-            const int stream_out = sizeof(T) * new_len > (size_t(192) << 20) ? 1 : 0; // (see the store loop of k_interp_inner)
+            const size_t lds2 = interp_inner_lds<T>(plan, is_complex);
+            const unsigned g = plan.g.inner_blocks;
+            const int stream_out = sizeof(T) * new_len > (size_t(192) << 20) ? 1 : 0; // (see the store loop of interp_inner_tile)
 #define BDSP_INNER2(FV, CP, QV)                                                                    \
     do {                                                                                           \
         auto kk = k_interp_inner<T, CP, FV, QV>;                                                   \
@@ -838,11 +1126,7 @@ int interpolatef_dev(const T* in, T* out, size_t len, bool is_complex, int fid, 
         return BDSP_OK;
     } else {
         const size_t tab_bytes = (size_t)2 * (2 * conv_len + 1) * sizeof(T);
-        // k_interp_scalar_v2 wherever the cos / sin table of the roll-off lattice fits 48 KB of LDS (every practical conv_len:
-        // up to 3071 taps a side in f32, 1535 in f64) and positions fit 32 bits; otherwise the first-generation kernel
-        // (tests/test_gpu_parity.py::test_interpolatef_fractional_factor_kernel_singularities_and_fallback runs both)
-        // at most 127 taps (the slow-pair mask is one 64-bit word; above: k_interp_scalar_v2)
-        if (2 * conv_len + 1 <= 127 && points < ((size_t)1 << 31)) {
+        if (plan.path == IF_FRAC_PK) {
             const unsigned long long slow = frac_slow_pairs(conv_len, (double)delay, fid, (double)rolloff);
             const size_t lds = sizeof(T) * 2 * ((2 * conv_len + 1 + 3) & ~(size_t)3);
             if (is_complex)
@@ -854,7 +1138,7 @@ int interpolatef_dev(const T* in, T* out, size_t len, bool is_complex, int fid, 
             BDSP_LAUNCH_CHECK();
             return BDSP_OK;
         }
-        if (tab_bytes <= 48 * 1024 && points < ((size_t)1 << 31)) {
+        if (plan.path == IF_SCALAR_V2) {
             if (is_complex)
                 hipLaunchKernelGGL((k_interp_scalar_v2<T, true>), dim3((unsigned)blocks), dim3(256), tab_bytes, s, in, out,
                                    (long long)points, (long long)new_points, (int)conv_len, factor, delay, fid, rolloff);
@@ -868,6 +1152,108 @@ int interpolatef_dev(const T* in, T* out, size_t len, bool is_complex, int fid, 
             hipLaunchKernelGGL((k_interp_scalar<T, false>), dim3((unsigned)blocks), dim3(256), 0, s, in, out,
                                (long long)points, (long long)new_points, (int)conv_len, factor, delay, fid, rolloff);
     }
+    BDSP_LAUNCH_CHECK();
+    return BDSP_OK;
+}
+
+// interpolatef of every row of a matrix (rows back to back, row_len scalars each -> interpolatef_new_len(row_len) scalars
+// each) in a number of launches that does not depend on `rows`: the plan of ONE row decides the path and the kernel, as
+// interpolatef_dev on that row would, and the kernels take the rows as a flat grid dimension.
+//   prm == null: every row with `delay` (divided by delta here); the cached tap table of the vector call.
+//   prm != null: row r with prm[r].delay (the caller has divided by delta) and, on the packed fractional path,
+//                prm[r].slow_pairs; the integer path's rows * f * ntaps taps go into the workspace by one launch.
+template <typename T>
+int mat_interpolatef_dev(const T* in, T* out, size_t rows, size_t row_len, bool is_complex, int fid, T rolloff, T factor,
+                         T delay, const InterpRowPrm<T>* prm, size_t conv_len_arg, T delta, hipStream_t s)
+{
+    const size_t elem = is_complex ? 2 : 1;
+    if (rows == 0 || row_len / elem == 0) return BDSP_OK;
+    if (!prm) delay = delay / delta;                          // interpolation.rs:397
+    const size_t cap = (size_t)num_cus() * 8;
+    const InterpPlan plan = interp_plan<T>(row_len, is_complex, factor, conv_len_arg, cap);
+    const size_t points = plan.points, conv_len = plan.conv_len, new_len = plan.new_len, new_points = plan.new_points;
+    if (new_points == 0) return BDSP_OK;
+    if (plan.simd) {
+        const int f = plan.f, ntaps = plan.ntaps;
+        const size_t tab = (size_t)ntaps * f, lds = sizeof(T) * tab;
+        if (lds > 60 * 1024) { set_last_error("interpolatef: tap table exceeds LDS"); return BDSP_ERR_UNSUPPORTED; }
+        WsBlock tb;
+        const T* taps_dev = nullptr;
+        size_t tap_stride = 0;
+        if (prm) {
+            const size_t total = rows * tab;
+            BDSP_TRY(tb.alloc(sizeof(T) * total, s));
+            hipLaunchKernelGGL((k_interp_taps<T, true>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, s, tb.as<T>(), fid, rolloff,
+                               (int)conv_len, f, (T)0, prm, total);
+            BDSP_LAUNCH_CHECK();
+            taps_dev = tb.as<T>();
+            tap_stride = tab;
+        } else {
+            BDSP_TRY(interp_tap_table<T>(fid, rolloff, (int)conv_len, f, delay, s, &tb, &taps_dev));
+        }
+        if (plan.path == IF_TABLE) {
+            const unsigned bpr = plan.g.edge_blocks;
+            size_t grid = rows * bpr;
+            if (grid > cap) grid = cap;
+            if (is_complex)
+                hipLaunchKernelGGL((k_mat_interpf_table<T, true>), dim3((unsigned)grid), dim3(256), lds, s, in, out, taps_dev,
+                                   (long long)points, (long long)new_points, (int)conv_len, f, rows, bpr, tap_stride);
+            else
+                hipLaunchKernelGGL((k_mat_interpf_table<T, false>), dim3((unsigned)grid), dim3(256), lds, s, in, out, taps_dev,
+                                   (long long)points, (long long)new_points, (int)conv_len, f, rows, bpr, tap_stride);
+        } else {
+            const long long q_lo = plan.g.q_lo, q_hi = plan.g.q_hi;
+            const unsigned g = plan.g.inner_blocks, eb = plan.g.edge_blocks;
+            constexpr int QB = sizeof(T) == 4 ? 2 : 1;   // complex
+            constexpr int QBR = sizeof(T) == 4 ? 4 : 2;  // real
+            const size_t lds2 = interp_inner_lds<T>(plan, is_complex);
+            size_t grid = rows * ((size_t)g + eb);
+            if (grid > cap) grid = cap;
+            const int stream_out = sizeof(T) * rows * new_len > (size_t(192) << 20) ? 1 : 0;
+#define BDSP_INNER2(FV, CP, QV)                                                                    \
+    do {                                                                                           \
+        auto kk = k_mat_interpf_inner<T, CP, FV, QV>;                                              \
+        if (lds2 > 64 * 1024)                                                                      \
+            BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2)); \
+        hipLaunchKernelGGL(kk, dim3((unsigned)grid), dim3(256), lds2, s, in, out, taps_dev, q_lo, q_hi, (int)conv_len, \
+                           (long long)points, (long long)new_points, g, eb, rows, tap_stride, stream_out); \
+    } while (0)
+#define BDSP_INNER(FV)                                                                             \
+    do {                                                                                           \
+        if (is_complex) BDSP_INNER2(FV, true, QB);                                                 \
+        else BDSP_INNER2(FV, false, QBR);                                                          \
+    } while (0)
+            if (f == 2) BDSP_INNER(2); else if (f == 3) BDSP_INNER(3); else if (f == 4) BDSP_INNER(4); else BDSP_INNER(8);
+#undef BDSP_INNER2
+#undef BDSP_INNER
+        }
+        BDSP_LAUNCH_CHECK();
+        return BDSP_OK;
+    }
+    // the scalar paths: a lane per flat output of rows * new_points
+    const size_t total = rows * new_points;
+    size_t blocks = (total + 255) / 256;
+    if (blocks > cap) blocks = cap;
+    const bool i32 = if_fits_32(rows * row_len, rows * new_len, rows, blocks * 256);
+    const unsigned long long slow = prm ? 0ull : frac_slow_pairs(conv_len, (double)delay, fid, (double)rolloff);
+    size_t lds = 0;
+    if (plan.path == IF_FRAC_PK) lds = sizeof(T) * 2 * ((2 * conv_len + 1 + 3) & ~(size_t)3);
+    else if (plan.path == IF_SCALAR_V2) lds = (size_t)2 * (2 * conv_len + 1) * sizeof(T);
+#define BDSP_ROWS2(CP, IDX)                                                                        \
+    do {                                                                                           \
+        if (plan.path == IF_FRAC_PK)                                                               \
+            hipLaunchKernelGGL((k_mat_interpf_frac_pk<T, CP, IDX>), dim3((unsigned)blocks), dim3(256), lds, s, in, out, (long long)points, \
+                               (long long)new_points, (int)conv_len, factor, delay, fid, rolloff, slow, rows, prm); \
+        else if (plan.path == IF_SCALAR_V2)                                                        \
+            hipLaunchKernelGGL((k_mat_interpf_scalar_v2<T, CP, IDX>), dim3((unsigned)blocks), dim3(256), lds, s, in, out, (long long)points, \
+                               (long long)new_points, (int)conv_len, factor, delay, fid, rolloff, rows, prm); \
+        else                                                                                       \
+            hipLaunchKernelGGL((k_mat_interpf_scalar<T, CP, IDX>), dim3((unsigned)blocks), dim3(256), 0, s, in, out, (long long)points, \
+                               (long long)new_points, (int)conv_len, factor, delay, fid, rolloff, rows, prm); \
+    } while (0)
+    if (is_complex) { if (i32) BDSP_ROWS2(true, unsigned); else BDSP_ROWS2(true, size_t); }
+    else { if (i32) BDSP_ROWS2(false, unsigned); else BDSP_ROWS2(false, size_t); }
+#undef BDSP_ROWS2
     BDSP_LAUNCH_CHECK();
     return BDSP_OK;
 }
@@ -1015,5 +1401,7 @@ BDSP_INST(double)
 
 template int interpolatef_dev<float>(const float*, float*, size_t, bool, int, float, float, float, size_t, float, hipStream_t, float (*)(const void*, float), const void*);
 template int interpolatef_dev<double>(const double*, double*, size_t, bool, int, double, double, double, size_t, double, hipStream_t, double (*)(const void*, double), const void*);
+template int mat_interpolatef_dev<float>(const float*, float*, size_t, size_t, bool, int, float, float, float, const InterpRowPrm<float>*, size_t, float, hipStream_t);
+template int mat_interpolatef_dev<double>(const double*, double*, size_t, size_t, bool, int, double, double, double, const InterpRowPrm<double>*, size_t, double, hipStream_t);
 
 } // namespace bdsp

@@ -446,7 +446,20 @@ class DspMat:
         return self._binary("correlate", other)
 
     def interpolatef(self, function, interpolation_factor, delay, conv_len, rolloff=0.0):
-        return self._call("interpolatef", int(function), rolloff, interpolation_factor, delay, int(conv_len))
+        """Every row resampled by `interpolation_factor` with wrap-around inside the row, as DspVec.interpolatef on that
+        row: rows become interpolatef_new_len points long, delta stays.  `delay` is one number for all rows, or a
+        one-dimensional sequence / array with one value per row (converted to the matrix's dtype): row r then equals
+        DspVec.interpolatef on row r with delay[r], bit for bit.  One launch for all rows (one more for the tap tables
+        of an integer factor), whatever their number.  Codes: 0; a delay sequence that does not have one value per row
+        leaves the matrix untouched and the code is 7.  -1 for a matrix that was poisoned before.  A matrix with no
+        rows or empty rows is left as it is (0).  (tests/test_gpu_mat_interpf.py holds the argument error.)"""
+        if np.ndim(delay) == 0:
+            return self._call("interpolatef", int(function), rolloff, interpolation_factor, delay, int(conv_len))
+        d = np.ascontiguousarray(delay, dtype=np.float32 if self._sfx == "32" else np.float64)
+        if d.ndim != 1:
+            raise ValueError("delay: a number or a one-dimensional sequence with one value per row")
+        ptr = d.ctypes.data_as(C.POINTER(C.c_float if self._sfx == "32" else C.c_double))
+        return self._call("interpolatef_delays", int(function), rolloff, interpolation_factor, ptr, d.size, int(conv_len))
 
     def multiply_frequency_response(self, function, ratio, rolloff=0.0):
         return self._call("multiply_frequency_response", int(function), rolloff, ratio)

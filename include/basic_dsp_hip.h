@@ -692,6 +692,14 @@ int32_t bdsp_hip_mat_convolve_signal_mat32(MatBuf32 *m, const VecBuf32 *const *i
                                            size_t count); /* :439-483: count == rows*rows, row-major [out][in] */
 int32_t bdsp_hip_mat_interpolatef32(MatBuf32 *m, int32_t impulse_response, float rolloff,
                                     float interpolation_factor, float delay, size_t conv_len);
+/* interpolatef with one delay per row: row r as bdsp_hip_interpolatef on it with delays[r] (each divided by the
+ * matrix's delta, as the vector call divides its delay); delta is left alone.  The launches do not depend on the row
+ * count.  Codes: 7 when count is not the row count or delays is null with count > 0 (the matrix is untouched); -1 for a
+ * poisoned matrix; 0 otherwise, a matrix with no rows or empty rows included.  The call uploads the delays, so it
+ * cannot be captured into a HIP graph (bdsp_hip_mat_interpolatef can, once its tap table is cached). */
+int32_t bdsp_hip_mat_interpolatef_delays32(MatBuf32 *m, int32_t impulse_response, float rolloff,
+                                           float interpolation_factor, const float *delays, size_t count,
+                                           size_t conv_len);
 int32_t bdsp_hip_mat_multiply_frequency_response32(MatBuf32 *m, int32_t frequency_response, float rolloff, float ratio);
 /* Per-row statistics, sums and dot products: one result per row in out[0 .. rows) (split: out[r*len + b], bucket b of
  * row r), one batched device pass.  `len` (split: `out_len`) must equal rows (rows * len), else 7; split len > 16 gives 7,
@@ -998,6 +1006,9 @@ int32_t bdsp_hip_mat_convolve_signal_mat64(MatBuf64 *m, const VecBuf64 *const *i
                                            size_t count); /* :439-483: count == rows*rows, row-major [out][in] */
 int32_t bdsp_hip_mat_interpolatef64(MatBuf64 *m, int32_t impulse_response, double rolloff,
                                     double interpolation_factor, double delay, size_t conv_len);
+int32_t bdsp_hip_mat_interpolatef_delays64(MatBuf64 *m, int32_t impulse_response, double rolloff,
+                                           double interpolation_factor, const double *delays, size_t count,
+                                           size_t conv_len);
 int32_t bdsp_hip_mat_multiply_frequency_response64(MatBuf64 *m, int32_t frequency_response, double rolloff, double ratio);
 /* per-row statistics, sums and dot products: as the f32 set above */
 int32_t bdsp_hip_mat_real_statistics64(const MatBuf64 *m, Statistics64 *out, size_t len);                 /* matrix/src/general/statistics.rs:4-19 */
