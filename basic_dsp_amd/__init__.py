@@ -7,5 +7,6 @@ benchmark and the multi-GPU batch driver; it has no CPU fallback.
 from ._lib import BackendError, Graph, LIB_PATH, lib, last_error, require_gpu  # noqa: F401
 from .vector import DspVec  # noqa: F401
 from .matrix import DspMat  # noqa: F401
+from .spectral import zoom_fft  # noqa: F401
 
-__all__ = ["DspVec", "DspMat", "Graph", "BackendError", "lib", "LIB_PATH", "last_error", "require_gpu"]
+__all__ = ["DspVec", "DspMat", "Graph", "BackendError", "lib", "LIB_PATH", "last_error", "require_gpu", "zoom_fft"]

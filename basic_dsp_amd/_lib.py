@@ -343,6 +343,11 @@ for _s, _t, _R in (("32", _F, VectorInteropResult32), ("64", _D, VectorInteropRe
     _proto(_m + "from_interleaved" + _s, C.c_int32, _P, _SZ, C.POINTER(_P))
     _proto(_m + "to_interleaved" + _s, C.c_int32, _P, C.POINTER(_P))
     _proto(_m + "zero_interleave" + _s, C.c_int32, _P, C.c_int32)
+    # chirp-z transform of a frequency band (spectral.zoom_fft): start and step are doubles in both precisions
+    if hasattr(lib, "bdsp_hip_zoom_fft" + _s):  # (an older build named by BDSP_HIP_LIBRARY for an A/B run has none)
+        _proto("bdsp_hip_zoom_fft" + _s, C.c_int32, _P, _D, _D, _SZ)
+        _proto(_m + "zoom_fft" + _s, C.c_int32, _P, _D, _D, _SZ)
+        _proto(_m + "zoom_fft_starts" + _s, C.c_int32, _P, C.POINTER(_D), _SZ, _D, _SZ)
 
 WINDOW_FN32 = C.CFUNCTYPE(_F, _P, _SZ, _SZ)
 WINDOW_FN64 = C.CFUNCTYPE(_D, _P, _SZ, _SZ)

@@ -366,5 +366,21 @@ template <typename T>
 int bs_post(const T* conv, T* out, const T* c, size_t n, size_t m, size_t batch, int out_kind, size_t rot,
             int div_window_id, T alpha, hipStream_t s);
 
+// zoom_fft.hip -- chirp-z transform of a band: rows x n points -> rows x bins complex, l = zf_conv_len(n, bins)
+// (zoom_fft_core.h); the launch counts do not depend on `rows`
+// the three tables of a plan: pre (n), post (bins) and the wrapped kernel (l, not yet transformed); start reduced modulo
+// 1 and step modulo 2 by the caller; one launch
+template <typename T>
+int zf_tables(T* pre, T* post, T* kern, size_t n, size_t bins, size_t l, double start, double step, hipStream_t s);
+// l in {512, 1024, 2048, 4096}: the whole transform in one launch; x (real scalars if in_real) and y must not overlap;
+// starts: null, or one start per row (device, reduced modulo 1) on top of a pre table built with start 0
+template <typename T>
+int zf_fused(const T* x, T* y, const T* pre, const T* post, const T* kspec, const double* starts, size_t n, size_t bins,
+             size_t l, size_t rows, bool in_real, hipStream_t s);
+// larger l: x -> rows x l complex (chirped, zero filled), and rows x l complex -> rows x bins (post-chirp, crop)
+template <typename T>
+int zf_pre(const T* x, T* a, const T* pre, const double* starts, size_t n, size_t l, size_t rows, bool in_real, hipStream_t s);
+template <typename T> int zf_post(const T* conv, T* out, const T* post, size_t bins, size_t l, size_t rows, hipStream_t s);
+
 // window value shared by fft.hip and elementwise.hip (device) -- defined inline in window.h
 } // namespace bdsp

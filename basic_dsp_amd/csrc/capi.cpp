@@ -18,6 +18,7 @@
 
 #include "bdsp_internal.h"
 #include "mat_frame_core.h"
+#include "zoom_fft_core.h"
 
 using namespace bdsp;
 
@@ -100,6 +101,11 @@ struct BsPlan {
     int esz = 0, dev = 0;
     unsigned long long stamp = 0;
     int pins = 0; // HIP graphs that recorded this plan's addresses: never evicted while > 0
+    // a zoom_fft plan (zf_plan): chirp holds the pre-chirp (n) and the post-chirp (bins) back to back, bspec the spectrum
+    // of the wrapped kernel; start and step as reduced by the caller.  A plain Bluestein plan has zoom == false.
+    bool zoom = false;
+    size_t bins = 0;
+    double start = 0, step = 0;
 };
 static std::mutex g_bs_mu;
 static std::vector<BsPlan> g_bs_plans;
@@ -121,13 +127,33 @@ struct GraphHandle {
 };
 constexpr size_t BS_CACHE_BYTES = size_t(1) << 30;
 
+// make room for a plan of `bytes` under the one budget of both plan kinds: least recently used plans go first (after the
+// device has drained their users)
+static int bs_make_room(size_t bytes)
+{
+    size_t used = 0;
+    for (auto& q : g_bs_plans) used += q.bytes;
+    while (!g_bs_plans.empty() && used + bytes > BS_CACHE_BYTES) {
+        size_t lru = g_bs_plans.size();
+        for (size_t i = 0; i < g_bs_plans.size(); ++i)
+            if (g_bs_plans[i].pins == 0 && (lru == g_bs_plans.size() || g_bs_plans[i].stamp < g_bs_plans[lru].stamp)) lru = i;
+        if (lru == g_bs_plans.size()) break; // everything left is pinned by a graph
+        BDSP_HIP_TRY(hipDeviceSynchronize());
+        (void)hipFree(g_bs_plans[lru].chirp);
+        (void)hipFree(g_bs_plans[lru].bspec);
+        used -= g_bs_plans[lru].bytes;
+        g_bs_plans.erase(g_bs_plans.begin() + (long)lru);
+    }
+    return BDSP_OK;
+}
+
 template <typename T>
 int bs_plan(size_t n, size_t m, bool inverse, hipStream_t s, const T** chirp, const T** bspec)
 {
     int dev = 0;
     BDSP_HIP_TRY(hipGetDevice(&dev));
     for (auto& p : g_bs_plans)
-        if (p.n == n && p.inverse == inverse && p.esz == (int)sizeof(T) && p.dev == dev) {
+        if (!p.zoom && p.n == n && p.inverse == inverse && p.esz == (int)sizeof(T) && p.dev == dev) {
             p.stamp = ++g_bs_clock;
             if (capturing_here()) { ++p.pins; g_capture_plans.push_back(p.chirp); }
             *chirp = (const T*)p.chirp;
@@ -142,20 +168,7 @@ int bs_plan(size_t n, size_t m, bool inverse, hipStream_t s, const T** chirp, co
     BsPlan p;
     p.n = n; p.m = m; p.inverse = inverse; p.esz = (int)sizeof(T); p.dev = dev;
     p.bytes = sizeof(T) * 2 * (n + m);
-    // make room: least recently used plans go first (after the device has drained their users)
-    size_t used = 0;
-    for (auto& q : g_bs_plans) used += q.bytes;
-    while (!g_bs_plans.empty() && used + p.bytes > BS_CACHE_BYTES) {
-        size_t lru = g_bs_plans.size();
-        for (size_t i = 0; i < g_bs_plans.size(); ++i)
-            if (g_bs_plans[i].pins == 0 && (lru == g_bs_plans.size() || g_bs_plans[i].stamp < g_bs_plans[lru].stamp)) lru = i;
-        if (lru == g_bs_plans.size()) break; // everything left is pinned by a graph
-        BDSP_HIP_TRY(hipDeviceSynchronize());
-        (void)hipFree(g_bs_plans[lru].chirp);
-        (void)hipFree(g_bs_plans[lru].bspec);
-        used -= g_bs_plans[lru].bytes;
-        g_bs_plans.erase(g_bs_plans.begin() + (long)lru);
-    }
+    BDSP_TRY(bs_make_room(p.bytes));
     BDSP_HIP_TRY(hipMalloc(&p.chirp, sizeof(T) * 2 * n));
     if (hipMalloc(&p.bspec, sizeof(T) * 2 * m) != hipSuccess) { (void)hipFree(p.chirp); set_last_error("hipMalloc failed"); return BDSP_ERR_HIP; }
     WsBlock scr;
@@ -173,6 +186,54 @@ int bs_plan(size_t n, size_t m, bool inverse, hipStream_t s, const T** chirp, co
     g_bs_plans.push_back(p);
     *chirp = (const T*)p.chirp;
     *bspec = (const T*)p.bspec;
+    return BDSP_OK;
+}
+
+// The tables of a zoom_fft (zoom_fft.hip) per (n, bins, start, step, precision, device), in the same cache, under the
+// same byte budget and capture rules as the Bluestein plans: *pre n complex, *post bins complex, *kspec the l-point
+// spectrum of the wrapped kernel.  start is reduced modulo 1 and step modulo 2 by the caller (g_bs_mu held).
+template <typename T>
+int zf_plan(size_t n, size_t bins, size_t l, double start, double step, hipStream_t s, const T** pre, const T** post,
+            const T** kspec)
+{
+    int dev = 0;
+    BDSP_HIP_TRY(hipGetDevice(&dev));
+    for (auto& p : g_bs_plans)
+        if (p.zoom && p.n == n && p.bins == bins && p.start == start && p.step == step && p.esz == (int)sizeof(T) && p.dev == dev) {
+            p.stamp = ++g_bs_clock;
+            if (capturing_here()) { ++p.pins; g_capture_plans.push_back(p.chirp); }
+            *pre = (const T*)p.chirp;
+            *post = (const T*)p.chirp + 2 * n;
+            *kspec = (const T*)p.bspec;
+            return BDSP_OK;
+        }
+    if (capturing_here()) {
+        // building a plan synchronises the stream (and may free memory): both would invalidate the open capture
+        set_last_error("chirp-z plan missing while a capture is open: run the sequence once before capturing it (warm the plan)");
+        return BDSP_ERR_UNSUPPORTED;
+    }
+    BsPlan p;
+    p.zoom = true;
+    p.n = n; p.m = l; p.bins = bins; p.start = start; p.step = step; p.esz = (int)sizeof(T); p.dev = dev;
+    p.bytes = sizeof(T) * 2 * (n + bins + l);
+    BDSP_TRY(bs_make_room(p.bytes));
+    BDSP_HIP_TRY(hipMalloc(&p.chirp, sizeof(T) * 2 * (n + bins)));
+    if (hipMalloc(&p.bspec, sizeof(T) * 2 * l) != hipSuccess) { (void)hipFree(p.chirp); set_last_error("hipMalloc failed"); return BDSP_ERR_HIP; }
+    WsBlock scr;
+    int c = scr.alloc(sizeof(T) * 2 * l, s);
+    if (c == BDSP_OK) c = zf_tables<T>((T*)p.chirp, (T*)p.chirp + 2 * n, (T*)p.bspec, n, bins, l, start, step, s);
+    bool rb = false;
+    if (c == BDSP_OK) c = fft_two_buffers<T>((T*)p.bspec, scr.as<T>(), l, 1, false, 0, (T)1, -1, (T)0, &rb, s);
+    if (c == BDSP_OK && rb &&
+        hipMemcpyAsync(p.bspec, scr.p, sizeof(T) * 2 * l, hipMemcpyDeviceToDevice, s) != hipSuccess) c = BDSP_ERR_HIP;
+    // the plan may be used from another stream next: finish building it first
+    if (c == BDSP_OK && hipStreamSynchronize(s) != hipSuccess) c = BDSP_ERR_HIP;
+    if (c != BDSP_OK) { (void)hipFree(p.chirp); (void)hipFree(p.bspec); return c; }
+    p.stamp = ++g_bs_clock;
+    g_bs_plans.push_back(p);
+    *pre = (const T*)p.chirp;
+    *post = (const T*)p.chirp + 2 * n;
+    *kspec = (const T*)p.bspec;
     return BDSP_OK;
 }
 
@@ -1854,6 +1915,73 @@ static bool mat_extent(size_t a, size_t b, size_t add, size_t elem, size_t* scal
     return true;
 }
 
+// zoom_fft (zoom_fft.hip): X[r][k] = sum_n x[r][n] exp(-2 pi i (start_r + k step) n), k < bins, for the `rows` rows of a
+// time-domain vector or matrix (a vector is one row); start_r = start, or starts[r] if per_row.  Nothing of it is in the
+// reference.  The result is complex, in the frequency domain, bins points per row, dense; delta <- step / delta.  An
+// argument error comes first (7, the data untouched); a poisoned input stays poisoned (the callers answer -1).  One launch
+// for convolution lengths up to 4096, else pre -> FFT_l -> x spectrum / l -> IFFT_l -> post, whatever the row count.
+// With per-row starts the call uploads them, so it cannot be captured into a HIP graph.
+template <typename T>
+int op_zoom_fft(DevVec<T>* v, size_t rows, double start, const double* starts, size_t count, bool per_row, double step,
+                size_t bins)
+{
+    if (bins == 0 || !std::isfinite(step)) return BDSP_ERR_ARG_LENGTH;
+    if (per_row) {
+        if (count != rows || (count > 0 && !starts)) return BDSP_ERR_ARG_LENGTH;
+        for (size_t r = 0; r < count; ++r)
+            if (!std::isfinite(starts[r])) return BDSP_ERR_ARG_LENGTH;
+    } else if (!std::isfinite(start)) return BDSP_ERR_ARG_LENGTH;
+    if (v->erroneous()) return BDSP_OK;
+    if (v->freq) return BDSP_ERR_MUST_BE_TIME;
+    // no rows, or rows of no points: as plain_fft leaves them
+    if (rows == 0) { v->valid_len = 0; v->complex_ = true; v->freq = true; return BDSP_OK; }
+    const size_t n = v->points() / rows;
+    if (n == 0) { v->complex_ = true; v->freq = true; return BDSP_OK; }
+    size_t total = 0, padded = 0;
+    if (!mat_extent(rows, bins, 0, 2, &total)) return BDSP_ERR_UNSUPPORTED;
+    const size_t l = zf_conv_len(n, bins);
+    if (l == 0) { set_last_error("zoom_fft: convolution length above 2^30"); return BDSP_ERR_UNSUPPORTED; }
+    if (!zf_is_fused(l) && !mat_extent(rows, l, 0, 2, &padded)) return BDSP_ERR_UNSUPPORTED;
+    hipStream_t s = lib_stream();
+    const bool in_real = !v->complex_;
+    // every phase is periodic: start modulo 1 (n is an integer), step modulo 2 (it multiplies j^2 / 2); + 0.0 folds -0 into 0
+    const double start_red = per_row ? 0.0 : fmod(start, 1.0) + 0.0, step_red = fmod(step, 2.0) + 0.0;
+    std::lock_guard<std::mutex> lk(g_bs_mu); // plans cannot be evicted between lookup and launch
+    const T *pre = nullptr, *post = nullptr, *kspec = nullptr;
+    BDSP_TRY(zf_plan<T>(n, bins, l, start_red, step_red, s, &pre, &post, &kspec));
+    WsBlock sb;
+    if (per_row) {
+        std::vector<double> red(rows);
+        for (size_t r = 0; r < rows; ++r) red[r] = fmod(starts[r], 1.0);
+        BDSP_TRY(sb.alloc(sizeof(double) * rows, s));
+        // (pageable memory: the copy has left `red` when the call returns)
+        BDSP_HIP_TRY(hipMemcpyAsync(sb.p, red.data(), sizeof(double) * rows, hipMemcpyHostToDevice, s));
+    }
+    BDSP_TRY(v->reserve(total));
+    if (zf_is_fused(l)) {
+        BDSP_TRY(zf_fused<T>(v->data, v->buf, pre, post, kspec, sb.as<double>(), n, bins, l, rows, in_real, s));
+    } else {
+        WsBlock wa, wt;
+        BDSP_TRY(wa.alloc(sizeof(T) * padded, s));
+        BDSP_TRY(wt.alloc(sizeof(T) * padded, s));
+        BDSP_TRY(zf_pre<T>(v->data, wa.as<T>(), pre, sb.as<double>(), n, l, rows, in_real, s));
+        bool ra = false;
+        BDSP_TRY(fft_two_buffers<T>(wa.as<T>(), wt.as<T>(), l, rows, false, 0, (T)1, -1, (T)0, &ra, s));
+        T* spec = ra ? wt.as<T>() : wa.as<T>();
+        T* scr = ra ? wa.as<T>() : wt.as<T>();
+        BDSP_TRY(mul_bcast<T>(spec, kspec, l, rows, (T)1 / (T)l, s));
+        bool rc = false;
+        BDSP_TRY(fft_two_buffers<T>(spec, scr, l, rows, true, 0, (T)1, -1, (T)0, &rc, s));
+        BDSP_TRY(zf_post<T>(rc ? scr : spec, v->buf, post, bins, l, rows, s));
+    }
+    v->trade();
+    v->valid_len = total;
+    v->complex_ = true;
+    v->freq = true;
+    v->delta = (T)(step / (double)v->delta);
+    return BDSP_OK;
+}
+
 template <typename T>
 void meta_copy(DevVec<T>* to, const DevVec<T>* from)
 {
@@ -3403,6 +3531,19 @@ BDSP_MAT_FRAME(64, double, MatBuf64, VecBuf64)
 BDSP_MAT_TRANSPOSE(32, float, MatBuf32, VecBuf32)
 BDSP_MAT_TRANSPOSE(64, double, MatBuf64, VecBuf64)
 #undef BDSP_MAT_TRANSPOSE
+
+// chirp-z transform of a frequency band (op_zoom_fft above): a vector is a matrix of one row
+#define BDSP_ZOOM_FFT(SFX, T, MB, VB)                                                                       \
+    int32_t bdsp_hip_zoom_fft##SFX(VB* vector, double start, double step, size_t bins)                      \
+    { DevVec<T>* v = H<T>(vector); return finish<T>(v, op_zoom_fft<T>(v, 1, start, nullptr, 0, false, step, bins)).result_code; } \
+    int32_t bdsp_hip_mat_zoom_fft##SFX(MB* m, double start, double step, size_t bins)                       \
+    { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_zoom_fft<T>(&a->v, a->rows, start, nullptr, 0, false, step, bins)); } \
+    int32_t bdsp_hip_mat_zoom_fft_starts##SFX(MB* m, const double* starts, size_t count, double step, size_t bins) \
+    { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_zoom_fft<T>(&a->v, a->rows, 0.0, starts, count, true, step, bins)); }
+
+BDSP_ZOOM_FFT(32, float, MatBuf32, VecBuf32)
+BDSP_ZOOM_FFT(64, double, MatBuf64, VecBuf64)
+#undef BDSP_ZOOM_FFT
 
 // ---------------------------------------------------------------------------------------------- B3
 int bdsp_hip_dev_fft(int elem, void* data, void* scratch, size_t points, size_t batch, unsigned flags,

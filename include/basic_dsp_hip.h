@@ -958,6 +958,22 @@ int32_t bdsp_hip_mat_transpose32(MatBuf32 *m);
 int32_t bdsp_hip_mat_from_interleaved32(const VecBuf32 *vector, size_t channels, MatBuf32 **out);
 int32_t bdsp_hip_mat_to_interleaved32(const MatBuf32 *m, VecBuf32 **out);
 int32_t bdsp_hip_mat_zero_interleave32(MatBuf32 *m, int32_t factor);
+/* zoom_fft: chirp-z transform of a frequency band (nothing of it is in the reference).  For every row x[0..N) of a
+ * time-domain vector or matrix (complex, or real read with a zero imaginary part)
+ *     X[k] = sum_{n<N} x[n] exp(-2 pi i (start + k step) n),   k = 0 .. bins-1
+ * start and step in cycles per sample, double in both precisions; unscaled, as plain_fft; step may be 0 or negative and
+ * bins may exceed N.  The result is complex, in the frequency domain, `bins` points per row, dense; delta becomes
+ * step / delta.  start = 0, step = 1/N, bins = N is plain_fft.  _starts takes one start per row (count == rows).
+ * Codes: 7 for bins == 0, a start or step that is not finite, count != rows or a null starts with count > 0 (the data
+ * are untouched); 5 for frequency-domain input; -1 for a poisoned vector or matrix; BDSP_ERR_UNSUPPORTED where
+ * rows * bins does not fit the address space or the convolution length -- the power of two >= N + bins - 1 -- is above
+ * 2^30.  No rows, or rows of no points: as plain_fft leaves them.  Convolution lengths up to 4096 are one launch.  The
+ * chirp tables are cached per (N, bins, start, step) with the chirp-z plans of the any-length transforms: inside a HIP
+ * graph capture a missing plan is BDSP_ERR_UNSUPPORTED (run the call once before), and _starts uploads its argument, so
+ * it cannot be captured at all. */
+int32_t bdsp_hip_zoom_fft32(VecBuf32 *v, double start, double step, size_t bins);
+int32_t bdsp_hip_mat_zoom_fft32(MatBuf32 *m, double start, double step, size_t bins);
+int32_t bdsp_hip_mat_zoom_fft_starts32(MatBuf32 *m, const double *starts, size_t count, double step, size_t bins);
 
 MatBuf64 *bdsp_hip_mat_new64(int32_t is_complex, int32_t domain, size_t rows, size_t row_len, double delta); /* row_len in scalars; zero filled */
 void bdsp_hip_mat_delete64(MatBuf64 *m);
@@ -1127,6 +1143,10 @@ int32_t bdsp_hip_mat_transpose64(MatBuf64 *m);
 int32_t bdsp_hip_mat_from_interleaved64(const VecBuf64 *vector, size_t channels, MatBuf64 **out);
 int32_t bdsp_hip_mat_to_interleaved64(const MatBuf64 *m, VecBuf64 **out);
 int32_t bdsp_hip_mat_zero_interleave64(MatBuf64 *m, int32_t factor);
+/* chirp-z transform of a frequency band: see bdsp_hip_zoom_fft32 */
+int32_t bdsp_hip_zoom_fft64(VecBuf64 *v, double start, double step, size_t bins);
+int32_t bdsp_hip_mat_zoom_fft64(MatBuf64 *m, double start, double step, size_t bins);
+int32_t bdsp_hip_mat_zoom_fft_starts64(MatBuf64 *m, const double *starts, size_t count, double step, size_t bins);
 
 /* ==========================================================================================
  * B3 -- kernels on caller-owned DEVICE memory.  `stream` is a hipStream_t passed as void*
