@@ -348,6 +348,9 @@ for _s, _t, _R in (("32", _F, VectorInteropResult32), ("64", _D, VectorInteropRe
         _proto("bdsp_hip_zoom_fft" + _s, C.c_int32, _P, _D, _D, _SZ)
         _proto(_m + "zoom_fft" + _s, C.c_int32, _P, _D, _D, _SZ)
         _proto(_m + "zoom_fft_starts" + _s, C.c_int32, _P, C.POINTER(_D), _SZ, _D, _SZ)
+    # the matrix product a . b / a . b^H (linalg.matmul): the result handle comes back through the last argument
+    if hasattr(lib, _m + "matmul" + _s):  # (as above)
+        _proto(_m + "matmul" + _s, C.c_int32, _P, _P, C.c_int32, C.POINTER(_P))
 
 WINDOW_FN32 = C.CFUNCTYPE(_F, _P, _SZ, _SZ)
 WINDOW_FN64 = C.CFUNCTYPE(_D, _P, _SZ, _SZ)

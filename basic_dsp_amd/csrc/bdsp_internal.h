@@ -355,6 +355,14 @@ int mf_rotate(const T* in, T* out, size_t rows, size_t points, size_t shift, boo
 template <typename T>
 int tp_transpose(const T* src, T* dst, size_t R, size_t C, bool is_complex, hipStream_t s);
 
+// mat_mul.hip -- out (M x N, dense) = a (M x K) . b (K x N), or a . b^H with b N x K if `trans`; elements are complex
+// pairs if is_complex; the path is mm_dispatch's (mat_mul_core.h).  scratch: mm_scratch_factor(M, N, K, trans) * M * N
+// elements (0 unless the split path runs: one launch, or two there).  out must not overlap a or b; a may be b
+size_t mm_scratch_factor(size_t M, size_t N, size_t K, bool trans);
+template <typename T>
+int mm_matmul(const T* a, const T* b, T* out, size_t M, size_t N, size_t K, bool is_complex, bool trans, T* scratch,
+              hipStream_t s);
+
 // bluestein.hip
 template <typename T> int bs_chirp(T* c, size_t n, bool inverse, hipStream_t s);
 template <typename T> int bs_kernel(const T* c, T* b, size_t n, size_t m, hipStream_t s);

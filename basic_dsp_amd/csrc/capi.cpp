@@ -2078,6 +2078,48 @@ int mat_transpose(DevMat<T>* m)
     return BDSP_OK;
 }
 
+// The matrix product (mat_mul.hip): out (M x N) = a (M x K) . b (K x N), or a . b^H with b N x K.  Nothing of it is in
+// the reference.  Sizes in points.  A poisoned operand comes first (a poisoned result, -1), then the number spaces (2),
+// then the shape (7).  Domain and delta of the result are those of the operand whose row axis survives: b in the plain
+// form, a in the transposed one.  One launch, or two on the split path, whatever the shape; a and b are only read and
+// may be the same object.
+template <typename T>
+int mat_matmul(const DevMat<T>* a, const DevMat<T>* b, bool trans, DevMat<T>** out)
+{
+    *out = nullptr;
+    const DevMat<T>* axis = trans ? a : b;
+    if (a->v.erroneous() || b->v.erroneous()) {
+        std::unique_ptr<DevMat<T>> m(new DevMat<T>());
+        meta_copy<T>(&m->v, &axis->v);
+        m->v.complex_ = a->v.complex_;
+        m->rows = a->rows;
+        m->v.poison();
+        BDSP_TRY(m->v.reserve(1));
+        *out = m.release();
+        return BDSP_ERR_POISONED;
+    }
+    if (a->v.complex_ != b->v.complex_) return BDSP_ERR_META_DATA;
+    const size_t M = a->rows, K = a->row_points(), N = trans ? b->rows : b->row_points();
+    if (K != (trans ? b->row_points() : b->rows)) return BDSP_ERR_ARG_LENGTH;
+    const size_t e = a->v.complex_ ? 2 : 1;
+    size_t total = 0, temp = 0;
+    if (!mat_extent(M, N, 0, e, &total)) return BDSP_ERR_UNSUPPORTED;
+    const size_t partials = mm_scratch_factor(M, N, K, trans);
+    if (partials && !mat_extent(total, partials, 0, 1, &temp)) return BDSP_ERR_UNSUPPORTED;
+    std::unique_ptr<DevMat<T>> m(new DevMat<T>());
+    meta_copy<T>(&m->v, &axis->v);
+    m->rows = M;
+    BDSP_TRY(m->v.reserve(total ? total : 1));
+    hipStream_t s = lib_stream();
+    if (total && K == 0) BDSP_HIP_TRY(hipMemsetAsync(m->v.data, 0, sizeof(T) * total, s)); // an empty sum: +0
+    WsBlock ws;
+    if (temp) BDSP_TRY(ws.alloc(sizeof(T) * temp, s));
+    BDSP_TRY(mm_matmul<T>(a->v.data, b->v.data, m->v.data, M, N, K, a->v.complex_, trans, ws.as<T>(), s));
+    m->v.valid_len = total;
+    *out = m.release();
+    return BDSP_OK;
+}
+
 // row c, point j = x[j * channels + c]: the transpose of the vector seen as [points / channels][channels]
 template <typename T>
 int mat_from_interleaved(const DevVec<T>* v, size_t channels, DevMat<T>** out)
@@ -3531,6 +3573,15 @@ BDSP_MAT_FRAME(64, double, MatBuf64, VecBuf64)
 BDSP_MAT_TRANSPOSE(32, float, MatBuf32, VecBuf32)
 BDSP_MAT_TRANSPOSE(64, double, MatBuf64, VecBuf64)
 #undef BDSP_MAT_TRANSPOSE
+
+// the matrix product a . b and a . b^H (mat_matmul above)
+#define BDSP_MAT_MATMUL(SFX, T, MB)                                                                         \
+    int32_t bdsp_hip_mat_matmul##SFX(const MB* a, const MB* b, int32_t b_conj_transposed, MB** out)         \
+    { DevMat<T>* m = nullptr; const int c = mat_matmul<T>(MC##SFX(a), MC##SFX(b), b_conj_transposed != 0, &m); *out = reinterpret_cast<MB*>(m); return c; }
+
+BDSP_MAT_MATMUL(32, float, MatBuf32)
+BDSP_MAT_MATMUL(64, double, MatBuf64)
+#undef BDSP_MAT_MATMUL
 
 // chirp-z transform of a frequency band (op_zoom_fft above): a vector is a matrix of one row
 #define BDSP_ZOOM_FFT(SFX, T, MB, VB)                                                                       \

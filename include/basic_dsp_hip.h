@@ -974,6 +974,26 @@ int32_t bdsp_hip_mat_zero_interleave32(MatBuf32 *m, int32_t factor);
 int32_t bdsp_hip_zoom_fft32(VecBuf32 *v, double start, double step, size_t bins);
 int32_t bdsp_hip_mat_zoom_fft32(MatBuf32 *m, double start, double step, size_t bins);
 int32_t bdsp_hip_mat_zoom_fft_starts32(MatBuf32 *m, const double *starts, size_t count, double step, size_t bins);
+/* matmul: the product of two matrices on the device (nothing of it is in the reference).  Sizes in POINTS.
+ *     b_conj_transposed == 0:  a: M x K, b: K x N  ->  out: M x N,  out[i][n] = sum_k a[i][k] * b[k][n]
+ *     b_conj_transposed != 0:  a: M x K, b: N x K  ->  out: M x N,  out[i][j] = sum_k a[i][k] * conj(b[j][k])
+ * a and b may be the same object (the Gram / covariance matrix of its rows); both stay untouched.  Both operands are
+ * real or both are complex (convert real weights with to_complex first); the result has their number space, and for real
+ * operands conj is the identity.  Domains and deltas need not agree: the result takes domain and delta from the operand
+ * whose row axis survives, b in the plain form and a in the transposed one.  A complex product is four real products.
+ * Codes: -1 for a poisoned a or b, with a poisoned result in *out; else 2 for a real and a complex operand; else 7
+ * unless a's row points equal b's rows (plain) or b's row points (transposed); after 2 and 7 *out = NULL.  Empty shapes
+ * return 0: K == 0 gives an M x N matrix of +0, M == 0 a matrix without rows, N == 0 M empty rows.  A failed allocation
+ * (BDSP_ERR_HIP) or a result or temporary too long for the address space (BDSP_ERR_UNSUPPORTED) returns that backend code
+ * with *out = NULL.  The call allocates its result (to be deleted by the caller with bdsp_hip_mat_delete), so it cannot
+ * be captured into a graph.  Rows of either operand may start on any element boundary.
+ * Deterministic: every output element is one sum over ascending k from +0 with one rounding per product; for K >= 256
+ * and at most 64 tiles of 64 x 64 outputs, K is cut into chunks whose sums are added in ascending chunk order.  The
+ * path and the order are a function of (M, N, K, number kind, precision, form) only, never of the device's CU count or
+ * of timing: the same call gives the same bits on every run.  With a == b in the transposed form the result is Hermitian
+ * to the bit and its diagonal has imaginary part +0.  Every element is within (2 K + 4) eps sum_k |a[i][k]| |b[k][n]| of
+ * the exact product.  One launch, or two where K is cut, whatever the shape. */
+int32_t bdsp_hip_mat_matmul32(const MatBuf32 *a, const MatBuf32 *b, int32_t b_conj_transposed, MatBuf32 **out);
 
 MatBuf64 *bdsp_hip_mat_new64(int32_t is_complex, int32_t domain, size_t rows, size_t row_len, double delta); /* row_len in scalars; zero filled */
 void bdsp_hip_mat_delete64(MatBuf64 *m);
@@ -1147,6 +1167,8 @@ int32_t bdsp_hip_mat_zero_interleave64(MatBuf64 *m, int32_t factor);
 int32_t bdsp_hip_zoom_fft64(VecBuf64 *v, double start, double step, size_t bins);
 int32_t bdsp_hip_mat_zoom_fft64(MatBuf64 *m, double start, double step, size_t bins);
 int32_t bdsp_hip_mat_zoom_fft_starts64(MatBuf64 *m, const double *starts, size_t count, double step, size_t bins);
+/* the product of two matrices: see bdsp_hip_mat_matmul32 */
+int32_t bdsp_hip_mat_matmul64(const MatBuf64 *a, const MatBuf64 *b, int32_t b_conj_transposed, MatBuf64 **out);
 
 /* ==========================================================================================
  * B3 -- kernels on caller-owned DEVICE memory.  `stream` is a hipStream_t passed as void*
