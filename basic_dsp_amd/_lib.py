@@ -351,6 +351,10 @@ for _s, _t, _R in (("32", _F, VectorInteropResult32), ("64", _D, VectorInteropRe
     # the matrix product a . b / a . b^H (linalg.matmul): the result handle comes back through the last argument
     if hasattr(lib, _m + "matmul" + _s):  # (as above)
         _proto(_m + "matmul" + _s, C.c_int32, _P, _P, C.c_int32, C.POINTER(_P))
+    # the Cholesky factorisation and the solves with its factor (linalg.cholesky, linalg.cholesky_solve)
+    if hasattr(lib, _m + "cholesky" + _s):  # (as above)
+        _proto(_m + "cholesky" + _s, C.c_int32, _P, _D, C.POINTER(_P))
+        _proto(_m + "cholesky_solve" + _s, C.c_int32, _P, _P, C.c_int32, C.POINTER(_P))
 
 WINDOW_FN32 = C.CFUNCTYPE(_F, _P, _SZ, _SZ)
 WINDOW_FN64 = C.CFUNCTYPE(_D, _P, _SZ, _SZ)

@@ -363,6 +363,17 @@ template <typename T>
 int mm_matmul(const T* a, const T* b, T* out, size_t M, size_t N, size_t K, bool is_complex, bool trans, T* scratch,
               hipStream_t s);
 
+// mat_chol.hip -- out (N x N, dense) = the lower Cholesky factor of a (only a's lower triangle and the real part of its
+// diagonal are read; loading is added to the diagonal as it is read); *flag (a zeroed device word) is non-zero afterwards
+// if a pivot was <= 0 or not finite.  scratch: la_chol_scratch(N) elements.  la_cholesky_solve: x (N x P) from the factor
+// l and b (N x P), part as LaPart (mat_chol_core.h); scratch: la_solve_scratch(N, P, part) elements.  x overlaps nothing
+size_t la_chol_scratch(size_t N);
+size_t la_solve_scratch(size_t N, size_t P, int part);
+template <typename T>
+int la_cholesky(const T* a, T* out, size_t N, bool is_complex, T loading, T* scratch, unsigned* flag, hipStream_t s);
+template <typename T>
+int la_cholesky_solve(const T* l, const T* b, T* x, size_t N, size_t P, bool is_complex, int part, T* scratch, hipStream_t s);
+
 // bluestein.hip
 template <typename T> int bs_chirp(T* c, size_t n, bool inverse, hipStream_t s);
 template <typename T> int bs_kernel(const T* c, T* b, size_t n, size_t m, hipStream_t s);

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "bdsp_internal.h"
+#include "mat_chol_core.h"
 #include "mat_frame_core.h"
 #include "zoom_fft_core.h"
 
@@ -2120,6 +2121,80 @@ int mat_matmul(const DevMat<T>* a, const DevMat<T>* b, bool trans, DevMat<T>** o
     return BDSP_OK;
 }
 
+// The Cholesky factorisation and the solves with its factor (mat_chol.hip).  Nothing of them is in the reference.  A
+// poisoned operand comes first (a poisoned result, -1), then the number spaces (2, the solve), then the shape (7).
+// mat_cholesky reads its flag word back after the last launch, the call's only synchronisation: 8 and no matrix for a
+// pivot <= 0 or not finite.  mat_cholesky_solve does not synchronise.
+template <typename T>
+static int la_poisoned_result(const DevMat<T>* like, size_t rows, DevMat<T>** out)
+{
+    std::unique_ptr<DevMat<T>> m(new DevMat<T>());
+    meta_copy<T>(&m->v, &like->v);
+    m->rows = rows;
+    m->v.poison();
+    BDSP_TRY(m->v.reserve(1));
+    *out = m.release();
+    return BDSP_ERR_POISONED;
+}
+
+template <typename T>
+int mat_cholesky(const DevMat<T>* a, double loading, DevMat<T>** out)
+{
+    *out = nullptr;
+    if (a->v.erroneous()) return la_poisoned_result<T>(a, a->rows, out);
+    const size_t N = a->rows;
+    if (N != a->row_points()) return BDSP_ERR_ARG_LENGTH;
+    const size_t e = a->v.complex_ ? 2 : 1;
+    size_t total = 0, temp = 0;
+    if (!mat_extent(N, N, 0, e, &total) || !mat_extent(la_chol_scratch(N), e, 0, 1, &temp)) return BDSP_ERR_UNSUPPORTED;
+    std::unique_ptr<DevMat<T>> m(new DevMat<T>());
+    meta_copy<T>(&m->v, &a->v);
+    m->rows = N;
+    BDSP_TRY(m->v.reserve(total ? total : 1));
+    m->v.valid_len = total;
+    if (N == 0) { *out = m.release(); return BDSP_OK; }
+    hipStream_t s = lib_stream();
+    WsBlock ws, flag;
+    if (temp) BDSP_TRY(ws.alloc(sizeof(T) * temp, s));
+    BDSP_TRY(flag.alloc(sizeof(unsigned), s));
+    BDSP_HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(unsigned), s));
+    BDSP_TRY(la_cholesky<T>(a->v.data, m->v.data, N, a->v.complex_, (T)loading, ws.as<T>(), flag.as<unsigned>(), s));
+    unsigned failed = 0;
+    BDSP_HIP_TRY(hipMemcpyAsync(&failed, flag.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    BDSP_HIP_TRY(hipStreamSynchronize(s));
+    if (failed) return BDSP_ERR_CONJ_SYMMETRIC; // 8: not the Hermitian positive-definite matrix the call needs
+    *out = m.release();
+    return BDSP_OK;
+}
+
+template <typename T>
+int mat_cholesky_solve(const DevMat<T>* l, const DevMat<T>* b, int part, DevMat<T>** out)
+{
+    *out = nullptr;
+    if (part != LA_PART_BOTH && part != LA_PART_FORWARD && part != LA_PART_BACKWARD) {
+        set_last_error("cholesky_solve: part is 0 (both), 1 (forward) or 2 (backward)");
+        return BDSP_ERR_UNSUPPORTED;
+    }
+    if (l->v.erroneous() || b->v.erroneous()) return la_poisoned_result<T>(b, b->rows, out);
+    if (l->v.complex_ != b->v.complex_) return BDSP_ERR_META_DATA;
+    const size_t N = l->rows, P = b->row_points();
+    if (N != l->row_points() || N != b->rows) return BDSP_ERR_ARG_LENGTH;
+    const size_t e = b->v.complex_ ? 2 : 1;
+    size_t total = 0, temp = 0;
+    if (!mat_extent(N, P, 0, e, &total) || !mat_extent(la_solve_scratch(N, P, part), e, 0, 1, &temp)) return BDSP_ERR_UNSUPPORTED;
+    std::unique_ptr<DevMat<T>> m(new DevMat<T>());
+    meta_copy<T>(&m->v, &b->v);
+    m->rows = N;
+    BDSP_TRY(m->v.reserve(total ? total : 1));
+    hipStream_t s = lib_stream();
+    WsBlock ws;
+    if (temp) BDSP_TRY(ws.alloc(sizeof(T) * temp, s));
+    BDSP_TRY(la_cholesky_solve<T>(l->v.data, b->v.data, m->v.data, N, P, b->v.complex_, part, ws.as<T>(), s));
+    m->v.valid_len = total;
+    *out = m.release();
+    return BDSP_OK;
+}
+
 // row c, point j = x[j * channels + c]: the transpose of the vector seen as [points / channels][channels]
 template <typename T>
 int mat_from_interleaved(const DevVec<T>* v, size_t channels, DevMat<T>** out)
@@ -3582,6 +3657,17 @@ BDSP_MAT_TRANSPOSE(64, double, MatBuf64, VecBuf64)
 BDSP_MAT_MATMUL(32, float, MatBuf32)
 BDSP_MAT_MATMUL(64, double, MatBuf64)
 #undef BDSP_MAT_MATMUL
+
+// the Cholesky factorisation and the solves with its factor (mat_cholesky, mat_cholesky_solve above)
+#define BDSP_MAT_CHOL(SFX, T, MB)                                                                           \
+    int32_t bdsp_hip_mat_cholesky##SFX(const MB* a, double loading, MB** out)                               \
+    { DevMat<T>* m = nullptr; const int c = mat_cholesky<T>(MC##SFX(a), loading, &m); *out = reinterpret_cast<MB*>(m); return c; } \
+    int32_t bdsp_hip_mat_cholesky_solve##SFX(const MB* l, const MB* b, int32_t part, MB** out)              \
+    { DevMat<T>* m = nullptr; const int c = mat_cholesky_solve<T>(MC##SFX(l), MC##SFX(b), part, &m); *out = reinterpret_cast<MB*>(m); return c; }
+
+BDSP_MAT_CHOL(32, float, MatBuf32)
+BDSP_MAT_CHOL(64, double, MatBuf64)
+#undef BDSP_MAT_CHOL
 
 // chirp-z transform of a frequency band (op_zoom_fft above): a vector is a matrix of one row
 #define BDSP_ZOOM_FFT(SFX, T, MB, VB)                                                                       \

@@ -1,5 +1,5 @@
-"""Dense linear algebra across the rows of DspMat: the matrix product.  A module-level function, like zoom_fft: DspVec
-and DspMat gain no method."""
+"""Dense linear algebra across the rows of DspMat: the matrix product, the Cholesky factorisation and the solves with its
+factor.  Module-level functions, like zoom_fft: DspVec and DspMat gain no method."""
 import ctypes as C
 
 from . import _lib
@@ -39,3 +39,66 @@ def matmul(a, b, conj_transpose=False):
     code = _lib.check(getattr(lib, "bdsp_hip_mat_matmul" + a._sfx)(a._h, b._h, int(bool(conj_transpose)), C.byref(out)),
                       "mat_matmul" + a._sfx)
     return code, (DspMat(_handle=out.value, _sfx=a._sfx) if out.value else None)
+
+
+_PARTS = {"both": 0, "forward": 1, "backward": 2}
+
+
+def cholesky(a, loading=0.0):
+    """(code, DspMat-or-None): the lower Cholesky factor L of a Hermitian positive-definite DspMat, a = L . L^H, on the
+    device.
+
+    a is N x N points, real (symmetric) or complex (Hermitian), f32 or f64.  Only the lower triangle is read, and of the
+    diagonal only the real part: the upper triangle and the diagonal's imaginary parts may hold anything, NaN included,
+    and do not change a bit of the result.  loading (a float) is rounded once to the matrix's precision and added to every
+    diagonal element as it is read, with one rounding: diagonal loading, R + s^2 I, the ordinary cure for a sample
+    covariance of fewer snapshots than channels.  a stays untouched.  L is a new N x N matrix: lower triangular, its
+    diagonal real and > 0 with imaginary part +0, every element above the diagonal +0, domain and delta from a.  With A the
+    loaded matrix, |A - L L^H| <= (2 N + 4) eps |L| |L|^H element by element.
+
+    Codes: 0; -1 for a poisoned operand (the result is poisoned too); 7 unless a.rows() == a.row_points() (no matrix); 8
+    when a pivot is <= 0 or not finite, so a is not the Hermitian positive-definite matrix the call needs (no matrix) --
+    one 4-byte read-back after the last launch, the only synchronisation of the call.  N == 0 gives 0 and an empty
+    matrix.  A failed allocation raises BackendError.  TypeError for anything that is not a DspMat.
+
+    Deterministic: the path and the order of operations depend on (N, number kind, precision) only, never on the device's
+    CU count or on timing; the same call gives the same bits on every run.  One launch for N <= 64, else blocks of 64 and
+    2 ceil(N / 64) - 1 launches.  Allocates its result, so it cannot be captured into a Graph."""
+    if not isinstance(a, DspMat):
+        raise TypeError("cholesky: a DspMat")
+    out = C.c_void_p()
+    code = _lib.check(getattr(lib, "bdsp_hip_mat_cholesky" + a._sfx)(a._h, float(loading), C.byref(out)), "mat_cholesky" + a._sfx)
+    return code, (DspMat(_handle=out.value, _sfx=a._sfx) if out.value else None)
+
+
+def cholesky_solve(l, b, part="both"):
+    """(code, DspMat-or-None): solve with a Cholesky factor on the device.  Sizes in points.
+
+        cholesky_solve(l, b)                    l: N x N, b: N x P  ->  X: N x P,  l l^H X = b   (A^-1 b)
+        cholesky_solve(l, b, part="forward")    l X = b      (L^-1 b: whitening)
+        cholesky_solve(l, b, part="backward")   l^H X = b    (L^-H b)
+
+    l is a factor as cholesky returns it; only its lower triangle is read, and of its diagonal only the real part.  "both"
+    is the forward pass followed by the backward pass, bit for bit.  X is a new matrix with domain and delta from b; both
+    operands stay untouched.  Element by element |b - l X| <= (2 N + 4) eps |l| |X| (forward; backward with l^H) and
+    |b - l l^H X| <= 3 (2 N + 4) eps |l| |l|^H |X| (both).
+
+    Codes: 0; -1 for a poisoned operand (the result is poisoned too); 2 for a real and a complex operand (no matrix); 7
+    unless l is square and l.rows() == b.rows() (no matrix).  P == 0 gives N empty rows, N == 0 a matrix without rows.  A
+    zero on l's diagonal gives inf / NaN in the result and code 0, as in any triangular solve: nothing is tested and
+    nothing is read back, so this call does not synchronise.  ValueError for any other part; TypeError for anything that
+    is not two DspMat of one precision; a failed allocation raises BackendError.
+
+    Deterministic: the path and the order of operations depend on (N, P, number kind, precision, part) only.  One launch
+    per triangular pass for N <= 64 (l in LDS, one thread per column of b, b read once and X written once), else
+    2 ceil(N / 64) - 1 launches per pass, whatever P.  Allocates its result, so it cannot be captured into a Graph."""
+    if not isinstance(l, DspMat) or not isinstance(b, DspMat):
+        raise TypeError("cholesky_solve: two DspMat")
+    if l._sfx != b._sfx:
+        raise TypeError("cholesky_solve: two DspMat of one precision")
+    if not isinstance(part, str) or part not in _PARTS:
+        raise ValueError("cholesky_solve: part is 'both', 'forward' or 'backward'")
+    out = C.c_void_p()
+    code = _lib.check(getattr(lib, "bdsp_hip_mat_cholesky_solve" + l._sfx)(l._h, b._h, _PARTS[part], C.byref(out)),
+                      "mat_cholesky_solve" + l._sfx)
+    return code, (DspMat(_handle=out.value, _sfx=l._sfx) if out.value else None)

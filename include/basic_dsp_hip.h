@@ -994,6 +994,32 @@ int32_t bdsp_hip_mat_zoom_fft_starts32(MatBuf32 *m, const double *starts, size_t
  * to the bit and its diagonal has imaginary part +0.  Every element is within (2 K + 4) eps sum_k |a[i][k]| |b[k][n]| of
  * the exact product.  One launch, or two where K is cut, whatever the shape. */
 int32_t bdsp_hip_mat_matmul32(const MatBuf32 *a, const MatBuf32 *b, int32_t b_conj_transposed, MatBuf32 **out);
+/* cholesky / cholesky_solve: Hermitian positive-definite systems on the device (nothing of them is in the reference).
+ * bdsp_hip_mat_cholesky: a is N x N, real (symmetric) or complex (Hermitian).  Only the lower triangle is read, and of
+ * the diagonal only the real part; the upper triangle and the diagonal's imaginary parts may hold anything, NaN included.
+ * loading is rounded once to the matrix's precision and added to every diagonal element as it is read, with one rounding
+ * (diagonal loading, a + loading I); a stays untouched.  *out is a new N x N matrix L with a = L L^H: lower triangular,
+ * the diagonal real and > 0 with imaginary part +0, every element above the diagonal +0, domain and delta from a.
+ * Codes: 0; -1 for a poisoned a, with a poisoned result in *out; else 7 unless a's rows equal its row points, *out =
+ * NULL; 8 when a pivot is <= 0 or not finite (a is not Hermitian positive definite), *out = NULL: one 4-byte read-back
+ * after the last launch, the call's only synchronisation.  N == 0 gives 0 and an empty matrix.  A failed allocation
+ * (BDSP_ERR_HIP) or a size too long for the address space (BDSP_ERR_UNSUPPORTED) returns that backend code with *out = NULL.
+ * bdsp_hip_mat_cholesky_solve: l is N x N, a factor as bdsp_hip_mat_cholesky returns it (only its lower triangle is read,
+ * of its diagonal the real part); b is N x P; *out is a new N x P matrix with domain and delta from b; both operands stay
+ * untouched.  part: 0 both (forward, then backward: a^-1 b), 1 forward (L x = b: L^-1 b, whitening), 2 backward
+ * (L^H x = b); any other value BDSP_ERR_UNSUPPORTED.  Codes: -1 for a poisoned l or b, with a poisoned result; else 2 for
+ * a real and a complex operand; else 7 unless l is square and l's rows equal b's rows; after 2 and 7 *out = NULL.  P == 0
+ * gives N empty rows, N == 0 a matrix without rows.  A zero on l's diagonal gives inf / NaN in the result and code 0;
+ * nothing is tested, nothing is read back: this call does not synchronise.
+ * Both calls allocate their results (to be deleted with bdsp_hip_mat_delete), so they cannot be captured into a graph.
+ * N <= 64: one launch (per triangular pass); larger N: blocks of 64, at most 3 ceil(N / 64) launches for the
+ * factorisation and 2 ceil(N / 64) per triangular pass, whatever P.  No atomics.  Deterministic: the path and the order
+ * of operations are a function of (N, P, number kind, precision, part) only, never of the device's CU count or of
+ * timing: the same call gives the same bits on every run.  Element-wise, with A the loaded matrix and c(N) = 2 N + 4:
+ * |A - L L^H| <= c(N) eps |L| |L|^H;  |b - L x| <= c(N) eps |L| |x| (forward; backward with L^H);
+ * |b - L L^H x| <= 3 c(N) eps |L| |L|^H |x| (both). */
+int32_t bdsp_hip_mat_cholesky32(const MatBuf32 *a, double loading, MatBuf32 **out);
+int32_t bdsp_hip_mat_cholesky_solve32(const MatBuf32 *l, const MatBuf32 *b, int32_t part, MatBuf32 **out);
 
 MatBuf64 *bdsp_hip_mat_new64(int32_t is_complex, int32_t domain, size_t rows, size_t row_len, double delta); /* row_len in scalars; zero filled */
 void bdsp_hip_mat_delete64(MatBuf64 *m);
@@ -1169,6 +1195,9 @@ int32_t bdsp_hip_mat_zoom_fft64(MatBuf64 *m, double start, double step, size_t b
 int32_t bdsp_hip_mat_zoom_fft_starts64(MatBuf64 *m, const double *starts, size_t count, double step, size_t bins);
 /* the product of two matrices: see bdsp_hip_mat_matmul32 */
 int32_t bdsp_hip_mat_matmul64(const MatBuf64 *a, const MatBuf64 *b, int32_t b_conj_transposed, MatBuf64 **out);
+/* Hermitian positive-definite systems: see bdsp_hip_mat_cholesky32 */
+int32_t bdsp_hip_mat_cholesky64(const MatBuf64 *a, double loading, MatBuf64 **out);
+int32_t bdsp_hip_mat_cholesky_solve64(const MatBuf64 *l, const MatBuf64 *b, int32_t part, MatBuf64 **out);
 
 /* ==========================================================================================
  * B3 -- kernels on caller-owned DEVICE memory.  `stream` is a hipStream_t passed as void*
