@@ -34,36 +34,17 @@
 //     reachable that way (a select-and-shuffle exchange of two other bits measured 625 ns), so a transform built on
 //     them needs radix 16 x 4 x 16 x 4 -- 55 more packed instructions per transform than 16 x 16 x 16 on the unit
 //     that is already the busiest; not built.
+//
+// The schedule -- the plan of a launch and the index arithmetic of the kernel -- lives in conv_v2_core.h, host+device,
+// and runs on the host in tests/host_sim/sim_conv_v2.cpp.
 #include "bdsp_internal.h"
+#include "conv_v2_core.h"
 #include <atomic>
 #include <type_traits>
 
 namespace bdsp {
 
-constexpr int L2 = 4096;
-
-template <typename T>
-struct ConvV2Args {
-    const cpx<T>* x;
-    cpx<T>* y;
-    const cpx<T>* hs;   // taps (hs_is_taps) or the UNSCALED, undelayed L-point spectrum of the taps
-    const cpx<T>* wtab; // exp(-2 pi i m / 4096)
-    unsigned n;      // points per vector
-    unsigned taps;
-    unsigned b_first, b_end; // blocks of each vector to compute
-    unsigned nb_lo, nb_hi;   // the interior ones among them: window inside [0, n), all V outputs below n
-    unsigned batch;
-    unsigned na, nbb;        // interior blocks (all vectors together) given to dispatch groups 0 and 1
-    int hs_is_taps;
-    unsigned groups;         // dispatch groups = workgroups per CU: 3 (f32), 2 (f64)
-};
-
-static __device__ __forceinline__ unsigned xcd_contiguous(unsigned bid, unsigned g)
-{
-    // workgroup w runs on XCD w % 8 (observed; only speed depends on it): give every XCD a contiguous run of the
-    // blocks of a round, so that the M-1 input samples neighbouring blocks share are an L2 hit
-    return (g & 7) == 0 ? (bid & 7) * (g >> 3) + (bid >> 3) : bid;
-}
+constexpr int L2 = CONV_V2_L;
 
 // f64 (round 2, late): the same structure with TWO workgroups per CU (74 KB of LDS and 240 registers each), two dispatch
 // groups, the generic padded exchange layouts and the six-value split of the stage-3 twiddles (fifteen would not fit).
@@ -160,7 +141,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void k_overlap_save_v2
     };
 
     // ---- the filter spectrum, delayed by d samples, x 1/L, in register r of thread t: H'[t + 256 r]
-    const unsigned d = OV - (a.taps - 1);
+    const unsigned d = conv_v2_delay(OV, a.taps);
     if (a.hs_is_taps) {
         C32 hv[16];
 #pragma unroll
@@ -188,10 +169,13 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void k_overlap_save_v2
         inverse(v);
     };
 
-    const long long in_off = -(long long)(a.taps / 2);
+    const long long in_off = -(long long)(a.taps / 2); // (conv_v2_in_off of conv_v2_core.h, inline: see the loop below)
     const unsigned G = gridDim.x;
     // ---- blocks that wrap around the ends of their vector (or whose outputs run past it): general code, taken first
     {
+        // (nw and b are conv_v2_wrap_count and conv_v2_wrap_block of conv_v2_core.h, left inline: through the functions
+        // hipcc sums nw in another order and the kernels' instructions change -- likewise in_off, lim and the group's
+        // lo / hi; change the header's copy with them)
         const unsigned nw = (a.nb_lo - a.b_first) + (a.b_end - a.nb_hi), total_w = nw * a.batch;
         for (unsigned w = blockIdx.x; w < total_w; w += G) {
             const unsigned vec = w / nw, k = w % nw;
@@ -203,8 +187,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void k_overlap_save_v2
                 T part[2][16];
 #pragma unroll
                 for (int half = 0; half < 2; ++half) {
-                    long long sb = ((long long)(2 * b + half) * V + in_off) % (long long)a.n;
-                    if (sb < 0) sb += a.n;
+                    const long long sb = conv_v2_window_start((long long)(2 * b + half), V, in_off, a.n);
 #pragma unroll
                     for (int r = 0; r < 16; ++r) part[half][r] = xr[((unsigned long long)sb + ut + 256u * r) % a.n];
                 }
@@ -213,8 +196,8 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void k_overlap_save_v2
                 transform(v);
 #pragma unroll
                 for (int half = 0; half < 2; ++half) {
-                    const long long obase = (long long)(2 * b + half) * V - OV;
-                    const long long room = (long long)a.n - obase;
+                    const long long obase = conv_v2_obase((long long)(2 * b + half), V, OV);
+                    const long long room = (long long)a.n - obase; // (lim: conv_v2_store_limit of conv_v2_core.h, inline: as above)
                     const unsigned lim = room <= 0 ? 0u : (room > L ? (unsigned)L : (unsigned)room);
                     T* yb = yr + obase;
 #pragma unroll
@@ -227,8 +210,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void k_overlap_save_v2
             }
             const C32* xv = a.x + (size_t)vec * a.n;
             C32* yv = a.y + (size_t)vec * a.n;
-            long long sb = ((long long)b * V + in_off) % (long long)a.n;
-            if (sb < 0) sb += a.n;
+            const long long sb = conv_v2_window_start((long long)b, V, in_off, a.n);
             const unsigned idx = (unsigned)sb + ut;
             if (a.n >= (unsigned)L) {
 #pragma unroll
@@ -243,8 +225,8 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void k_overlap_save_v2
             }
             transform(v);
             // z[np], OV <= np < OV + V, is output b V + np - OV; only outputs below n exist
-            const long long obase = (long long)b * V - OV;
-            const long long room = (long long)a.n - obase;
+            const long long obase = conv_v2_obase((long long)b, V, OV);
+            const long long room = (long long)a.n - obase; // (lim: conv_v2_store_limit of conv_v2_core.h, inline: as above)
             const unsigned lim = room <= 0 ? 0u : (room > L ? (unsigned)L : (unsigned)room);
             C32* yb = yv + obase;
 #pragma unroll
@@ -258,6 +240,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void k_overlap_save_v2
     const unsigned ni = a.nb_hi - a.nb_lo, total = ni * a.batch, gs = G / a.groups;
     const unsigned grp = blockIdx.x / gs;
     if (grp >= a.groups) return;
+    // (conv_v2_group_lo and conv_v2_group_hi of conv_v2_core.h, inline: as above)
     const unsigned lo = grp == 0 ? 0u : (grp == 1 ? a.na : a.na + a.nbb);
     const unsigned hi = grp == 0 ? a.na : ((grp == 1 && a.groups == 3) ? a.na + a.nbb : total);
     // (Round 3, measured and NOT adopted: RUNS of consecutive blocks per workgroup.  Block b + 1's first R0 rows are block
@@ -269,11 +252,11 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void k_overlap_save_v2
     // pass, whereas the strided sweep below leaves one compact window.)
     const unsigned w2 = xcd_contiguous(blockIdx.x - grp * gs, gs);
     for (unsigned id = lo + w2; id < hi; id += gs) {
-        unsigned vec = 0, b = a.nb_lo + id;
-        if (BATCHED) { vec = id / ni; b = a.nb_lo + id % ni; }
+        unsigned vec, b;
+        conv_v2_split_id<BATCHED>(id, ni, a.nb_lo, vec, b);
         if constexpr (REAL) {
             const T* x0 = reinterpret_cast<const T*>(a.x) + ((size_t)vec * a.n + ((long long)(2 * b) * V + in_off));
-            T* y0 = reinterpret_cast<T*>(a.y) + ((size_t)vec * a.n + ((long long)(2 * b) * V - OV));
+            T* y0 = reinterpret_cast<T*>(a.y) + ((size_t)vec * a.n + conv_v2_obase((long long)(2 * b), V, OV));
             C32 v[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) v[r] = C32{x0[ut + 256u * r], x0[V + ut + 256u * r]};
@@ -286,7 +269,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 3 : 2) void k_overlap_save_v2
             continue;
         }
         const C32* xb = a.x + ((size_t)vec * a.n + ((long long)b * V + in_off));
-        C32* yb = a.y + ((size_t)vec * a.n + ((long long)b * V - OV));
+        C32* yb = a.y + ((size_t)vec * a.n + conv_v2_obase((long long)b, V, OV));
         C32 v[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) v[r] = xb[ut + 256u * r];
@@ -352,8 +335,7 @@ thread_local int t_conv_share_a = -1, t_conv_share_b = -1;
 // block step of the second-generation kernel: V = 4096 - 256 ceil((M-1)/256)
 size_t conv_v2_block_step(size_t taps)
 {
-    const size_t r0 = taps <= 1 ? 1 : (taps - 1 + 255) / 256;
-    return (size_t)L2 - 256 * r0;
+    return (size_t)L2 - 256 * (size_t)conv_v2_r0(taps);
 }
 
 void conv_v2_set_shares(int first_pct, int second_pct)
@@ -364,7 +346,7 @@ void conv_v2_set_shares(int first_pct, int second_pct)
 
 bool conv_v2_applies(size_t points, size_t taps)
 {
-    return taps >= 1 && taps - 1 <= 3 * (size_t)L2 / 4 && points >= 1 && points < (size_t(1) << 31);
+    return taps >= 1 && conv_v2_r0(taps) <= CONV_V2_MAX_R0 && points >= 1 && points < (size_t(1) << 31);
 }
 #endif
 
@@ -376,26 +358,16 @@ int conv_v2_run(const T* in, T* out, size_t points, size_t batch, const T* hs, s
 {
     const cpx<T>* wtab;
     BDSP_TRY(twiddle_table<T>(L2, &wtab));
-    const unsigned r0 = taps <= 1 ? 1u : (unsigned)((taps - 1 + 255) / 256);
-    const long long V = L2 - 256 * (long long)r0;
-    const long long U = real ? 2 : 1; // real blocks per kernel block
-    const long long nb_all = (((long long)points + V - 1) / V + U - 1) / U;
-    long long b0 = (long long)first_block, b1 = nblocks ? b0 + (long long)nblocks : nb_all;
-    if (b1 > nb_all) b1 = nb_all;
-    if (b0 >= b1 || batch == 0) return BDSP_OK;
-    const long long in_off = -(long long)(taps / 2);
-    // interior blocks: window [bV + in_off, + L) inside [0, n) (then all V outputs are below n as well, see below)
-    long long lo = b0, hi = b1;
-    // (a pair is interior when both of its real blocks are: the first one's window start and the last one's end decide)
-    while (lo < hi && lo * U * V + in_off < 0) ++lo;
-    while (hi > lo && ((hi * U - 1) * V + in_off + L2 > (long long)points || (hi * U - 1) * V + V > (long long)points)) --hi;
-    if ((unsigned long long)(b1 - b0) * batch >= (1ull << 32) || batch > 0xffffffffull) {
+    constexpr unsigned GROUPS = sizeof(T) == 4 ? 3 : 2; // what the kernel's register budget allows per CU
+    // (bdsp_hip_dev_convolve_ex overrides the percentages for its own call: the guard test times equal shares against these)
+    const ConvV2Plan p = conv_v2_plan(points, taps, batch, first_block, nblocks, real, num_cus(), GROUPS, t_conv_share_a, t_conv_share_b);
+    if (p.status == CONV_V2_PLAN_NOTHING) return BDSP_OK;
+    if (p.status == CONV_V2_PLAN_TOO_MANY) {
         set_last_error("convolve_overlap_save: too many blocks");
         return BDSP_ERR_UNSUPPORTED;
     }
-    constexpr unsigned GROUPS = sizeof(T) == 4 ? 3 : 2; // what the kernel's register budget allows per CU
     ConvV2Args<T> a{};
-    a.groups = GROUPS;
+    conv_v2_set_geometry(a, p, points, taps, batch, GROUPS);
     // A complex result larger than the Infinity Cache can hold until its reader comes is streamed past the caches
     // 
     const bool nts = !real && conv_v2_streams_result<T>(points, batch);
@@ -403,40 +375,10 @@ int conv_v2_run(const T* in, T* out, size_t points, size_t batch, const T* hs, s
     a.y = reinterpret_cast<cpx<T>*>(out);
     a.hs = reinterpret_cast<const cpx<T>*>(hs);
     a.wtab = wtab;
-    a.n = (unsigned)points;
-    a.taps = (unsigned)taps;
-    a.b_first = (unsigned)b0; a.b_end = (unsigned)b1;
-    a.nb_lo = (unsigned)lo; a.nb_hi = (unsigned)hi;
-    a.batch = (unsigned)batch;
     a.hs_is_taps = hs_is_taps ? 1 : 0;
-    // grid: GROUPS workgroups per CU, a multiple of 8 * GROUPS so that every dispatch group is a multiple of 8
-    const unsigned long long interior = (unsigned long long)(hi - lo) * batch;
-    const unsigned long long wrap = (unsigned long long)((lo - b0) + (b1 - hi)) * batch;
-    const unsigned Q = 8 * GROUPS;
-    unsigned grid = (unsigned)num_cus() * GROUPS;
-    grid -= grid % Q;
-    if (grid < Q) grid = Q;
-    if (interior + wrap < grid) { // a small problem: no more workgroups than blocks (each one transforms the taps first)
-        grid = (unsigned)((interior + wrap + Q - 1) / Q * Q);
-        if (grid < Q) grid = Q;
-    }
-    const unsigned gs = grid / GROUPS;
-    // shares in whole rounds of gs blocks.  Three groups: ~43 % / ~37 % / rest (measured optimum 9 / 8 / 4.3 rounds of
-    // 21.3); two groups: ~55 % / rest (12 of 21.3 rounds measured best for two workgroups per CU)
-    const unsigned long long rounds = (interior + gs - 1) / gs;
-    // (bdsp_hip_dev_convolve_ex overrides the percentages for its own call: the guard test times equal shares against these)
-    const int sa = t_conv_share_a, sb = t_conv_share_b;
-    const unsigned long long pa = sa > 0 ? (unsigned long long)sa : (GROUPS == 3 ? 43 : 55);
-    const unsigned long long pb = GROUPS == 3 ? (sa > 0 ? (unsigned long long)sb : 37) : 0;
-    unsigned long long ra = (rounds * pa + 50) / 100, rb = (rounds * pb + 50) / 100;
-    if (rounds && ra == 0) ra = 1;
-    unsigned long long na = ra * gs, nbb = rb * gs;
-    if (na > interior) na = interior;
-    if (na + nbb > interior) nbb = interior - na;
-    a.na = (unsigned)na;
-    a.nbb = (unsigned)nbb;
+    const unsigned grid = p.grid;
     const size_t lds = (size_t)(sizeof(T) == 4 ? WgFft<T, L2, 256>::LDS_ELEMS3 : WgFft<T, L2, 256>::LDS_ELEMS + 16 * 17) * sizeof(cpx<T>);
-    switch (r0) {
+    switch (p.r0) {
 #define BDSP_R0(N) case N: return launch_v2<T, N>(a, grid, lds, s, real, nts);
         BDSP_R0(1) BDSP_R0(2) BDSP_R0(3) BDSP_R0(4) BDSP_R0(5) BDSP_R0(6)
         BDSP_R0(7) BDSP_R0(8) BDSP_R0(9) BDSP_R0(10) BDSP_R0(11) BDSP_R0(12)
