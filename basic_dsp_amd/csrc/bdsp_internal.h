@@ -11,6 +11,7 @@
 
 #include "../../include/basic_dsp_hip.h"
 #include "fft_core.h"
+#include "fft_plan_core.h"
 
 namespace bdsp {
 
@@ -88,25 +89,7 @@ template <typename T> int twiddle_table(int n, const cpx<T>** table);
 template <typename T> bool twiddle_table_available(int n); // cached already, or the cache still has room
 
 // ---------------------------------------------------------------- fused FFT prologue / epilogue
-template <typename T>
-struct FftIo {
-    const void* in;
-    void* out;
-    size_t n;          // points per vector
-    size_t in_stride;  // elements (of the input element type) between consecutive batch vectors
-    size_t out_stride; // elements (of the output element type) between consecutive batch vectors
-    unsigned flags;    // BDSP_FFT_* (SHIFT_IN, SHIFT_OUT, MAGNITUDE) + internal bits below
-    T in_scale;        // applied to every input element (1 = none)
-    int window_id;     // -1 none; else reference window id (4 = Hann)
-    T window_alpha;
-    size_t in_valid;   // 0 = all n points; else points >= in_valid read as zero (fused End zero-padding)
-    // cos / sin of q * 2 pi (n/16) / (n-1), q = 0..7: a pass thread's sixteen rows are n/16 points apart, so a generalised
-    // Hamming window costs it two sincospi and sixteen multiply-adds (filled by launch_pass; k_fft_pass, round 4)
-    T win_c[8], win_s[8];
-};
-constexpr unsigned FFT_IN_REAL = 1u << 8;        // input is a real vector (zero imaginary parts)
-constexpr unsigned FFT_WINDOW_OUT_DIV = 1u << 9; // divide OUTPUT by the window (windowed_ifft)
-constexpr unsigned FFT_OUT_REAL = 1u << 10;      // write only the real parts
+// FftIo and the internal flag bits FFT_IN_REAL / FFT_WINDOW_OUT_DIV / FFT_OUT_REAL: fft_plan_core.h (no HIP call in there)
 
 // ---------------------------------------------------------------- kernel launchers (per .hip TU)
 // fft.hip

@@ -58,9 +58,10 @@ int fft_two_buffers(T* a, T* b, size_t points, size_t batch, bool inverse, unsig
         else io.out = a;
         return fft_pow2<T>(io, nullptr, nullptr, batch, inverse, s);
     }
-    const bool three = fft_pow2_passes<T>(points) == 3;
+    // the order of the buffers: fft_buffer_order (fft_plan_core.h)
+    const int order = fft_buffer_order(sizeof(T), points, flags);
     io.in = a;
-    if (!three) { // a -> b -> a
+    if (order != FFT_BUF_ABAB) { // a -> b -> a
         io.out = a;
         // a -> b -> b from 2^19 points on: the last pass reads and writes the same index set per workgroup, so it may run in
         // place, and the working set of that pass halves.  *Measured* on valid data, input AND scratch cold / input in the
@@ -70,7 +71,7 @@ int fft_two_buffers(T* a, T* b, size_t points, size_t batch, bool inverse, unsig
         // 2^21 37.3 -> 36.6 / =, 2^22 69.6 -> 66.9 / 46.4 -> 47.2, 16 x 2^20 f64 218.8 -> 214.0 / 213.5 -> 203.2, 64 x 2^20 f32 equal.
         // Below 2^19 nothing moves (2^14 ... 2^18: +-0.2 us) except batches, which LOSE (256 x 2^16 f32: 83.5 -> 97-100 us with the
         // input in the caches), and 2^24's third pass in place measured 135 against 128 us (below).
-        if (!reshaping && points >= (size_t(1) << 19)) {
+        if (order == FFT_BUF_ABB) {
             io.out = b;
             *in_b = true;
             return fft_pow2<T>(io, b, nullptr, batch, inverse, s);
@@ -894,15 +895,7 @@ int op_complex_to_real(DevVec<T>* v, int kind)
     return BDSP_OK;
 }
 
-// window ids: facade ids 0..3 (interop/src/lib.rs:153-164, unknown -> rectangular) + 4 = Hann
-template <typename T>
-void map_window(int id, int* wid, T* alpha)
-{
-    *alpha = (T)0.54;
-    if (id == 4) { *wid = 1; *alpha = (T)0.5; }
-    else if (id >= 0 && id <= 3) *wid = id;
-    else *wid = 3;
-}
+// (map_window, the facade's window ids: fft_plan_core.h)
 
 // plain_fft / fft / windowed_fft (time_to_freq.rs:136-176) and plain_ifft / ifft / windowed_ifft
 // (freq_to_time.rs:136-177) with the shift, window and 1/N scale fused into the transform.
@@ -918,27 +911,13 @@ int op_fft(DevVec<T>* v, bool inverse, bool shift, int window /* -1 none */, siz
         if (!v->freq) { v->poison(); v->complex_ = true; v->freq = true; return BDSP_OK; } // :142-147
     }
     if (rows == 0) { v->valid_len = 0; v->complex_ = true; v->freq = !inverse; return BDSP_OK; } // a matrix without rows
-    unsigned flags = 0;
     size_t points = v->points() / rows;
-    if (!v->complex_) { // real input is zero-interleaved to complex first (:147-150)
-        flags |= FFT_IN_REAL;
-        BDSP_TRY(v->reserve(2 * v->valid_len));
-    }
-    int wid = -1;
-    T alpha = 0;
-    T in_scale = (T)1;
-    if (!inverse) {
-        if (window >= 0) map_window<T>(window, &wid, &alpha);
-        if (shift) flags |= BDSP_FFT_SHIFT_OUT;
-    } else if (shift) {
-        // ifft = scale(1/points) -> ifft_shift -> plain_ifft (freq_to_time.rs:160-168)
-        in_scale = (T)1 / (T)points;
-        flags |= BDSP_FFT_SHIFT_IN;
-        if (window >= 0) { map_window<T>(window, &wid, &alpha); flags |= FFT_WINDOW_OUT_DIV; }
-    }
+    if (!v->complex_) BDSP_TRY(v->reserve(2 * v->valid_len)); // real input is zero-interleaved to complex first (:147-150)
+    // the operation as transform options: fft_op_args (fft_plan_core.h)
+    const FftOpArgs<T> a = fft_op_args<T>(inverse, shift, window, !v->complex_, points);
     if (points == 0) { v->complex_ = true; v->freq = !inverse; return BDSP_OK; }
     bool in_b = false;
-    BDSP_TRY(fft_two_buffers<T>(v->data, v->buf, points, rows, inverse, flags, in_scale, wid, alpha, &in_b, s));
+    BDSP_TRY(fft_two_buffers<T>(v->data, v->buf, points, rows, inverse, a.flags, a.in_scale, a.window_id, a.window_alpha, &in_b, s));
     if (in_b) v->trade();
     v->valid_len = 2 * points * rows;
     v->complex_ = true;

@@ -37,8 +37,8 @@
 namespace bdsp {
 
 template <typename T>
-int launch_pass_opts_rp(int rp, int w, const FftIo<T>& io, const cpx<T>* src, cpx<T>* dst, size_t n, size_t nsg, size_t batch,
-                        bool inverse, bool first, bool last, hipStream_t s);
+int launch_pass_opts_rp(const FftPassRoute& r, const FftIo<T>& io, const cpx<T>* src, cpx<T>* dst, size_t n, size_t nsg, size_t batch,
+                        hipStream_t s);
 template <typename T>
 int launch_wg_gen(int n, const FftIo<T>& io, size_t batch, bool inverse, hipStream_t s);
 
@@ -97,64 +97,7 @@ __device__ __forceinline__ void io_store(const FftIo<T>& io, size_t vec, size_t 
         reinterpret_cast<cpx<T>*>(io.out)[vec * io.out_stride + dst] = v;
 }
 
-// LDS stride (in elements) between the regions of adjacent columns / transforms of one workgroup.
-// Lanes that run along columns hit addresses c*stride + const: with the padded length alone the
-// stride is a multiple of 16 elements = a multiple of 32 banks, i.e. a 16-way conflict (measured:
-// 90 % of LDS cycles were conflict cycles).  stride = 16*k + max(1, 16/W) spreads the W columns of a
-// 16-lane group over all banks, and leaves room for the rows of a second thread-row when W < 16.
-__host__ __device__ constexpr int col_stride(int n, int w = 0)
-{
-    int nt = n / 16 > 0 ? n / 16 : 1;
-    if (w == 0) w = 256 / nt;
-    int padded = n + (n >> 4);
-    int base = (padded + 15) / 16 * 16;
-    return base + (w >= 16 ? 1 : 16 / w);
-}
-
-// Inner-stage twiddles of a pass kernel from an LDS copy of the RP-entry table instead of global memory?  Yes whenever
-// the copy does not cost a resident workgroup.  *Measured* on 64 x 2^20 points (two passes of 1024-point columns):
-// 479 us with the 27 dependent global loads per thread and tile between an LDS gather and its butterflies, 405 us with
-// the loads removed altogether (a timing experiment); keeping the twiddles in registers across a persistent tile
-// loop instead made hipcc allocate 200+ VGPRs (532 us) or, with the budget capped at 128, spill (890 us).
-__host__ __device__ constexpr int pass_wgs_per_cu(size_t lds_bytes, int threads)
-{
-    size_t k = (size_t)(160 * 1024) / (lds_bytes + 64);
-    if (k > (size_t)(2048 / threads)) k = (size_t)(2048 / threads);
-    if (k > 8) k = 8;
-    return (int)k;
-}
-// SPLIT exchange (round 3): an f64 tile of 2048 x 4 or 1024 x 8 points is 136 KB of LDS -- ONE 512-thread workgroup per
-// CU, which loads, transforms and stores its tile with nothing to overlap any phase (config C4a's 4M points are two such
-// tiles per CU in all).  These tiles therefore cross their real and imaginary parts one after the other through a
-// buffer of HALF the size (8-byte elements: twice the LDS instructions and barriers, the same bytes), which lets two
-// workgroups share a CU.  Not for the GEN instantiations, which stage whole complex values through the buffer.
-template <typename T, int RP, int W, bool GEN>
-constexpr bool pass_split_exchange()
-{
-    return !GEN && sizeof(T) == 8 && (size_t)W * col_stride(RP, W) * sizeof(cpx<T>) > 80 * 1024;
-}
-template <typename T, int RP, int W, bool GEN>
-constexpr size_t pass_tile_lds_bytes()
-{
-    return (size_t)W * col_stride(RP, W) * (pass_split_exchange<T, RP, W, GEN>() ? sizeof(T) : sizeof(cpx<T>));
-}
-
-// waves per SIMD the pass kernel is compiled for: the split tiles want two 512-thread workgroups per CU = 4 (128 VGPRs)
-template <typename T, int RP, int W, bool GEN>
-constexpr int pass_min_waves()
-{
-    return pass_split_exchange<T, RP, W, GEN>() ? 2 * (W * (RP / 16)) / 256 : 1;
-}
-
-template <typename T, int RP, int W, bool GEN = true>
-constexpr bool pass_lds_twiddles()
-{
-    constexpr size_t base = pass_tile_lds_bytes<T, RP, W, GEN>(), tab = (size_t)RP * sizeof(cpx<T>);
-    // ... and always for the 4-wide 1024-point f32 tiles: the plan picks them only when the launch has fewer than two
-    // tiles per CU (one 2^20-point vector: 256 tiles), where the fourth resident workgroup the table costs is never there
-    if (sizeof(T) == 4 && RP == 1024 && W == 4) return true;
-    return RP >= 256 && pass_wgs_per_cu(base, W * (RP / 16)) == pass_wgs_per_cu(base + tab, W * (RP / 16));
-}
+// (col_stride, pass_split_exchange, pass_tile_lds_bytes, pass_min_waves, pass_lds_twiddles: fft_plan_core.h)
 
 // ------------------------------------------------------------------------------ n <= 8
 template <typename T, int N, int DIR>
@@ -706,29 +649,7 @@ __global__ __launch_bounds__(W * (RP / 16), (pass_min_waves<T, RP, W, GEN>())) v
 // (one 2^20-point f32 vector as two half-column launches, k_fft_half512: measured slower, round 4 -- docs/HISTORY.md A)
 
 // ------------------------------------------------------------------------------ launchers
-// plain complex in/out with the natural batch stride and no fused option?  The input side and the
-// output side are judged separately so that e.g. fft->magnitude pays the staged path only in its
-// last pass.
-template <typename T>
-static bool io_in_generic(const FftIo<T>& io)
-{
-    // ifft_shift (a register renaming for even n) and the input scale are handled by the plain path
-    // ... and so is a generalised Hamming window on the first global pass (n > 4096)
-    // (... and so are all four reference windows -- the rectangular one multiplies by one -- on the first global pass)
-    const bool win = io.window_id >= 0 && !(io.flags & FFT_WINDOW_OUT_DIV) && !(io.window_id <= 3 && io.n > 4096);
-    // ... and real input (zero imaginary parts)
-    return win || io.in_stride != io.n || (io.in_valid != 0 && io.n > 4096);
-}
-template <typename T>
-static bool io_out_generic(const FftIo<T>& io)
-{
-    // fft_shift is handled by the plain path
-    // ... and magnitude / real-part outputs are written straight from the registers
-    // ... and so is the division by one of the reference's windows (windowed_ifft) on the last global pass
-    return ((io.flags & FFT_WINDOW_OUT_DIV) != 0 && !(io.window_id >= 0 && io.window_id <= 3 && io.n > 4096)) || io.out_stride != io.n;
-}
-template <typename T>
-static bool io_is_generic(const FftIo<T>& io) { return io_in_generic(io) || io_out_generic(io); }
+// (plain or generic I/O -- io_in_generic, io_out_generic, io_is_generic -- is decided in fft_plan_core.h)
 
 template <typename T>
 static size_t wg_lds_bytes(int n)
@@ -839,28 +760,21 @@ static int launch_tiny(const FftIo<T>& io, size_t batch, bool inverse, hipStream
     return BDSP_OK;
 }
 
-// first-pass tiles that read their (dead) input with non-temporal loads: f64, whole 128-byte lines per row (launch_pass)
+// One global pass as fft_pass_route (fft_plan_core.h) describes it: this function only picks the instantiation the route
+// names; it decides nothing itself.
 template <typename T, int RP, int W>
-constexpr bool pass_ntl_candidate()
-{
-    return sizeof(T) == 8 && (size_t)W * sizeof(cpx<T>) >= 128;
-}
-
-// tiles the plans use as a FIRST pass only: their later-pass instantiations are not built
-template <int RP, int W>
-constexpr bool pass_first_only()
-{
-    return RP == 4096;
-}
-
-template <typename T, int RP, int W>
-static int launch_pass(const FftIo<T>& io_in, const cpx<T>* src, cpx<T>* dst, size_t n, size_t nsg,
-                       size_t batch, bool inverse, bool first, bool last, hipStream_t s)
+static int launch_pass(const FftPassRoute& r, const FftIo<T>& io_in, const cpx<T>* src, cpx<T>* dst, size_t n, size_t nsg,
+                       size_t batch, hipStream_t s)
 {
     FftIo<T> io = io_in;
     const cpx<T>* const src0 = src;
     cpx<T>* const dst0 = dst;
     (void)src0; (void)dst0; // (used by the plain unit only, BDSP_FFT_PART == 1)
+    const bool first = r.rowmap, last = r.last, inverse = r.dir > 0;
+    if (r.rp != RP || r.w != W || r.rowmap != (nsg == 1) || r.threads != W * (RP / 16) || r.grid != (n / RP) / W * batch) {
+        set_last_error("fft pass: route and launch disagree");
+        return BDSP_ERR_UNSUPPORTED;
+    }
     if ((first || last) && (io.window_id == 1 || io.window_id == 2) && n > 1) {
         // the window constants of k_fft_pass: cos / sin of q * 2 pi (n/16) / (n-1), q = 0..7, from double precision
         const double step = 2.0 * (double)(n / 16) / ((double)n - 1.0); // in units of pi
@@ -872,21 +786,19 @@ static int launch_pass(const FftIo<T>& io_in, const cpx<T>* src, cpx<T>* dst, si
     const cpx<T>* wtab;
     BDSP_TRY(twiddle_table<T>(RP, &wtab));
     constexpr int THREADS = W * (RP / 16);
-    size_t tiles = (n / RP) / W;
-    dim3 grid((unsigned)(tiles * batch));
-    const bool rowmap = nsg == 1; // the first pass
-    const bool gen = (first && io_in_generic(io)) || (last && io_out_generic(io));
+    const size_t tiles = r.tiles_per_vec;
+    dim3 grid((unsigned)r.grid);
+    const bool rowmap = r.rowmap; // the first pass
+    const bool gen = r.gen;
     // (triangular / Blackman-Harris on a split-exchange f64 tile: the kernel instantiated for that window, see k_fft_pass)
-    const bool win_here = io.window_id >= 0 && ((first && !(io.flags & FFT_WINDOW_OUT_DIV)) || (last && (io.flags & FFT_WINDOW_OUT_DIV)));
-    const int win_fixed = (!gen && win_here && pass_split_exchange<T, RP, W, false>() && (io.window_id == 0 || io.window_id == 2)) ? io.window_id : -1;
+    const int win_fixed = r.win_fixed;
     (void)win_fixed; // (the plain unit sends every windowed pass to the options unit)
     if (first && !gen) src = reinterpret_cast<const cpx<T>*>(io.in);
     if (last && !gen) dst = reinterpret_cast<cpx<T>*>(io.out);
     // plain first / last pass?  (then no option is looked at inside the kernel)
-    const bool simple = !gen && (rowmap ? ((io.flags & (FFT_IN_REAL | BDSP_FFT_SHIFT_IN)) == 0 && io.in_scale == (T)1 && io.window_id < 0)
-                                        : (!last || (io.flags & (BDSP_FFT_SHIFT_OUT | BDSP_FFT_MAGNITUDE | FFT_OUT_REAL | FFT_WINDOW_OUT_DIV)) == 0));
+    const bool simple = r.simple;
 #if BDSP_FFT_PART == 1
-    if (!simple) return launch_pass_opts_rp<T>(RP, W, io_in, src0, dst0, n, nsg, batch, inverse, first, last, s); // the options unit
+    if (!simple) return launch_pass_opts_rp<T>(r, io_in, src0, dst0, n, nsg, batch, s); // the options unit
 #endif
     // Non-temporal loads in the FIRST pass of an f64 transform whose tile reads whole 128-byte lines (W >= 8: the 3-pass plans'
     // 256 x 16 / 128 x 32 tiles, the 1024 x 8 / 512 x 8 tiles of batches and of 2^18 points).  *Measured* (round 5, cold / input in
@@ -895,11 +807,12 @@ static int launch_pass(const FftIo<T>& io_in, const cpx<T>* src, cpx<T>* dst, si
     // 2^18 equal.  NOT where the tile reads half lines (2^21 / 2^22 f64 single vectors: cold 36.6 -> 33.7 / 67.2 -> 60.8 but with
     // the input in the caches 28.1 -> 32.5 / 46.1 -> 62.3 -- every half line becomes a fetch of its own), and not in f32, where it
     // is a wash or worse (2^23 -5 % cold, 2^24 -6 % cold / +1 % hot, 2^25 +6 %, 64 x 2^20 +8 %, 4096 x 2^14 +1 %).
-    const bool ntl = pass_ntl_candidate<T, RP, W>() && first && rowmap && !gen && !(io.flags & FFT_IN_REAL);
+    const bool ntl = r.ntl;
 #define BDSP_PASS_K(DIRV, RM, GENV, SV, WINV, NTLV)                                                 \
     do {                                                                                           \
         constexpr size_t lds = pass_tile_lds_bytes<T, RP, W, GENV>() +                             \
                                (pass_lds_twiddles<T, RP, W, GENV>() ? (size_t)RP * sizeof(cpx<T>) : 0); \
+        if (lds != r.lds_bytes) { set_last_error("fft pass: route and kernel disagree on LDS"); return BDSP_ERR_UNSUPPORTED; } \
         BDSP_TRY(set_lds(k_fft_pass<T, RP, W, DIRV, RM, GENV, SV, WINV, NTLV>, lds));              \
         hipLaunchKernelGGL((k_fft_pass<T, RP, W, DIRV, RM, GENV, SV, WINV, NTLV>), grid, dim3(THREADS), lds, s, \
                            io, src, dst, wtab, n, nsg, tiles, (int)last);                          \
@@ -950,16 +863,17 @@ static int launch_pass(const FftIo<T>& io_in, const cpx<T>* src, cpx<T>* dst, si
     return BDSP_OK;
 }
 
-// (super-radix, tile width) pairs that are instantiated.  Default tile: W = 4096/RP columns
-// (256 threads); the wider variants trade LDS for longer contiguous global segments.
+// (super-radix, tile width) pairs that are instantiated: the ones pass_tile_built (fft_plan_core.h) names.  Default tile:
+// W = 4096/RP columns (256 threads); the wider variants trade LDS for longer contiguous global segments.
 template <typename T>
-static int launch_pass_rp(int rp, int w, const FftIo<T>& io, const cpx<T>* src, cpx<T>* dst,
-                          size_t n, size_t nsg, size_t batch, bool inverse, bool first, bool last,
-                          hipStream_t s)
+static int launch_pass_rp(const FftPassRoute& r, const FftIo<T>& io, const cpx<T>* src, cpx<T>* dst,
+                          size_t n, size_t nsg, size_t batch, hipStream_t s)
 {
 #define BDSP_CASE(RPV, WV)                                                                         \
-    if (rp == RPV && w == WV)                                                                      \
-        return launch_pass<T, RPV, WV>(io, src, dst, n, nsg, batch, inverse, first, last, s);
+    if (r.rp == RPV && r.w == WV) {                                                                \
+        static_assert(pass_tile_built(sizeof(T), RPV, WV), "pass_tile_built lists the instantiated tiles"); \
+        return launch_pass<T, RPV, WV>(r, io, src, dst, n, nsg, batch, s);                         \
+    }
     // every pair plan_passes can choose
     BDSP_CASE(64, 64) BDSP_CASE(128, 32) BDSP_CASE(256, 16) BDSP_CASE(512, 8) BDSP_CASE(1024, 4)
     BDSP_CASE(1024, 8) BDSP_CASE(2048, 4)
@@ -971,55 +885,7 @@ static int launch_pass_rp(int rp, int w, const FftIo<T>& io, const cpx<T>* src, 
     return BDSP_ERR_UNSUPPORTED;
 }
 
-// Super-radix plan for n = 2^bits > 4096: 2 passes up to 2^20, 3 passes up to 2^30, bits split as
-// evenly as possible, largest first (the first pass is the one whose stores are always long
-// contiguous runs, so it can afford the narrowest tile).
-static int plan_passes(size_t n, size_t batch, size_t esz, int rp[3], int w[3])
-{
-    int bits = 0;
-    while ((size_t(1) << bits) < n) ++bits;
-    if (bits > 30) return 0;
-    // 2^21 and 2^22 points: two passes of long columns beat three fully coalesced ones although their runs are only 32-64
-    // bytes.  Round 5, re-measured on VALID data with input and scratch cold / input in the caches
-    // (profiles/r05_plan_probe_valid.txt; the figures of rounds 2-3 came from loops that transformed their own output, i.e.
-    // inf / NaN), last pass in place:
-    //   2^21 f32  1024x8 + 2048x4  24.3 / 19.8 us   (2048x4 + 1024x8 24.6 / 19.2; three passes 30.3 / 26.9 out of place)
-    //   2^22 f32  4096x4 + 1024x8  40.4 / 32.3      (2048x4 + 2048x4, the plan until round 5: 42.9 / 33.3; three passes 41.4 / 34.0)
-    //   2^21 f64  1024x4 + 2048x4  36.6 / 28.4      (three passes 39.5 / 34.5)
-    //   2^22 f64  2048x4 + 2048x4  66.9 / 47.0      (2048x2 + 2048x4 70.8 / 50.8; three passes 76.5 / 65.6)
-    // From 2^23 on three passes win on a cold input: f32 71.2 / 65.7 against 78.9-86.7 / 63.3-63.8 for the 4096-point
-    // columns, f64 137.9 / 131.1 against 140-147 / 121-132; 2^24 f32 132.5 / 129.2 against 173 / 149.
-    if (bits == 21 || bits == 22) {
-        if (esz == 4) {
-            if (bits == 21) { rp[0] = 1024; w[0] = 8; rp[1] = 2048; w[1] = 4; }
-            else { rp[0] = 4096; w[0] = 4; rp[1] = 1024; w[1] = 8; }
-        } else {
-            rp[0] = bits == 21 ? 1024 : 2048; rp[1] = 2048;
-            w[0] = 4; w[1] = 4; // 2^22 f64: 2-wide first-pass tiles are no faster plain (above) and 7 us slower with a fused window
-        }
-        return 2;
-    }
-    int passes = bits <= 20 ? 2 : 3;
-    int base = bits / passes, extra = bits % passes;
-    for (int i = 0; i < passes; ++i) {
-        rp[i] = 1 << (base + (i < extra ? 1 : 0));
-        w[i] = 4096 / rp[i];
-        // 1024-point columns: 8-wide tiles (64-byte segments, 512 threads) measured 14 % faster than
-        // 4-wide ones on 64 x 2^20 points; 2-pass plans for 2^24 (4096x2 / 4096x4 tiles) measured
-        // 30-70 % SLOWER than three fully coalesced 256-point passes, so 3 passes stay.
-        // ... unless that leaves fewer tiles than two per CU (a single 2^20-point vector has 128):
-        // then 4-wide tiles fill the chip (measured 19.8 -> 17.2 us for one 2^20-point transform)
-        if (rp[i] == 1024) w[i] = (n * batch / 8192 >= (size_t)2 * num_cus()) ? 8 : 4;
-    }
-    return passes;
-}
-
-// lengths whose PLAIN transform (no fused option) runs in the one-workgroup kernel k_fft_wg4 instead of two passes
-template <typename T>
-static bool wg4_serves(size_t n)
-{
-    return sizeof(T) == 4 && n == 8192;
-}
+// (the plan -- how many passes, which tiles, when the one-workgroup kernel serves -- is fft_plan of fft_plan_core.h)
 
 // Runs the transform described by `io` on power-of-two n.  io.in holds the input.  For n <= 4096
 // the result goes to io.out (io.out may equal io.in unless the input is real).  For n > 4096 the
@@ -1051,17 +917,18 @@ int fft_pow2(const FftIo<T>& io, T* scratch_a, T* scratch_b, size_t batch, bool 
     case 4096: return launch_wg<T, 4096>(io, batch, inverse, s);
     default: break;
     }
+    const FftPlan plan = fft_plan(sizeof(T), n, batch, num_cus(), io.flags, io.in_scale != (T)1, io.window_id, io.in_stride,
+                                  io.out_stride, io.in_valid, inverse);
+    const int passes = plan.passes;
     if constexpr (sizeof(T) == 4) {
         // *measured*: 8192 points, batch 2048: 94.8 us as two passes, 73.3 us in one workgroup each (batch 256:
         // 19.8 -> 13.2 us, a single transform 7.7 vs 7.9 us); the 16384-point instantiation (1024 threads, one
         // workgroup per CU) measured SLOWER than two passes at every batch size and is not built
-        // (wg4_serves: the one predicate this dispatch and bdsp_hip_fft_passes share, above)
-        if (wg4_serves<T>(n) && !io_is_generic(io) && io.window_id < 0 &&
-            !(io.flags & (BDSP_FFT_MAGNITUDE | FFT_OUT_REAL | FFT_IN_REAL))) return launch_wg4<T, 8192>(io, batch, inverse, s);
+        // (wg4_takes: the predicate this dispatch and bdsp_hip_fft_passes share, fft_plan_core.h)
+        if (passes == 1) return launch_wg4<T, 8192>(io, batch, inverse, s);
     }
-    int rp[3], w[3];
-    int passes = plan_passes(n, batch, sizeof(T), rp, w);
     if (passes == 0) { set_last_error("FFT length above 2^30 points"); return BDSP_ERR_UNSUPPORTED; }
+    if (passes == 1) { set_last_error("fft_pow2: no one-workgroup kernel for this precision"); return BDSP_ERR_UNSUPPORTED; }
     if (!scratch_a || (passes == 3 && !scratch_b)) {
         set_last_error("fft_pow2: scratch missing");
         return BDSP_ERR_UNSUPPORTED;
@@ -1071,14 +938,14 @@ int fft_pow2(const FftIo<T>& io, T* scratch_a, T* scratch_b, size_t batch, bool 
     size_t nsg = 1;
     // (the intermediate in natural order: a tiled layout, one contiguous block per second-pass tile, measured no faster --
     // round 4, profiles/r04_fft_tiled_intermediate.txt: the narrow reads were never the cost, its scattered stores are one)
-    BDSP_TRY(launch_pass_rp<T>(rp[0], w[0], io, nullptr, sa, n, nsg, batch, inverse, true, false, s));
-    nsg *= rp[0];
+    BDSP_TRY(launch_pass_rp<T>(plan.r[0], io, nullptr, sa, n, nsg, batch, s));
+    nsg *= plan.r[0].rp;
     if (passes == 2) {
-        BDSP_TRY(launch_pass_rp<T>(rp[1], w[1], io, sa, nullptr, n, nsg, batch, inverse, false, true, s));
+        BDSP_TRY(launch_pass_rp<T>(plan.r[1], io, sa, nullptr, n, nsg, batch, s));
     } else {
-        BDSP_TRY(launch_pass_rp<T>(rp[1], w[1], io, sa, sb, n, nsg, batch, inverse, false, false, s));
-        nsg *= rp[1];
-        BDSP_TRY(launch_pass_rp<T>(rp[2], w[2], io, sb, nullptr, n, nsg, batch, inverse, false, true, s));
+        BDSP_TRY(launch_pass_rp<T>(plan.r[1], io, sa, sb, n, nsg, batch, s));
+        nsg *= plan.r[1].rp;
+        BDSP_TRY(launch_pass_rp<T>(plan.r[2], io, sb, nullptr, n, nsg, batch, s));
     }
     return BDSP_OK;
 }
@@ -1089,8 +956,7 @@ template <typename T>
 int fft_pow2_passes(size_t n)
 {
     if (n <= 4096) return 1;
-    int rp[3], w[3];
-    return plan_passes(n, 1, sizeof(T), rp, w);
+    return plan_pass_count(n, sizeof(T));
 }
 
 template <typename T>
@@ -1103,10 +969,10 @@ int fft_pow2_plain_trips(size_t n)
 #if BDSP_FFT_PART != 1
 // the options unit's two entry points (with BDSP_FFT_PART == 0 they are defined here too and simply never called)
 template <typename T>
-int launch_pass_opts_rp(int rp, int w, const FftIo<T>& io, const cpx<T>* src, cpx<T>* dst, size_t n, size_t nsg, size_t batch,
-                        bool inverse, bool first, bool last, hipStream_t s)
+int launch_pass_opts_rp(const FftPassRoute& r, const FftIo<T>& io, const cpx<T>* src, cpx<T>* dst, size_t n, size_t nsg, size_t batch,
+                        hipStream_t s)
 {
-    return launch_pass_rp<T>(rp, w, io, src, dst, n, nsg, batch, inverse, first, last, s);
+    return launch_pass_rp<T>(r, io, src, dst, n, nsg, batch, s);
 }
 template <typename T>
 int launch_wg_gen(int n, const FftIo<T>& io, size_t batch, bool inverse, hipStream_t s)
@@ -1128,8 +994,8 @@ int launch_wg_gen(int n, const FftIo<T>& io, size_t batch, bool inverse, hipStre
 }
 #endif
 #if BDSP_FFT_PART == 2
-template int launch_pass_opts_rp<BDSP_FFT_T>(int, int, const FftIo<BDSP_FFT_T>&, const cpx<BDSP_FFT_T>*, cpx<BDSP_FFT_T>*, size_t, size_t, size_t, bool, bool,
-                                             bool, hipStream_t);
+template int launch_pass_opts_rp<BDSP_FFT_T>(const FftPassRoute&, const FftIo<BDSP_FFT_T>&, const cpx<BDSP_FFT_T>*, cpx<BDSP_FFT_T>*, size_t, size_t, size_t,
+                                             hipStream_t);
 template int launch_wg_gen<BDSP_FFT_T>(int, const FftIo<BDSP_FFT_T>&, size_t, bool, hipStream_t);
 #else
 template int fft_pow2<BDSP_FFT_T>(const FftIo<BDSP_FFT_T>&, BDSP_FFT_T*, BDSP_FFT_T*, size_t, bool, hipStream_t);
