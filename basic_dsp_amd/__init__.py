@@ -8,7 +8,7 @@ from ._lib import BackendError, Graph, LIB_PATH, lib, last_error, require_gpu  #
 from .vector import DspVec  # noqa: F401
 from .matrix import DspMat  # noqa: F401
 from .spectral import zoom_fft  # noqa: F401
-from .linalg import matmul, cholesky, cholesky_solve  # noqa: F401
+from .linalg import matmul, cholesky, cholesky_solve, eigh  # noqa: F401
 
 __all__ = ["DspVec", "DspMat", "Graph", "BackendError", "lib", "LIB_PATH", "last_error", "require_gpu", "zoom_fft",
-           "matmul", "cholesky", "cholesky_solve"]
+           "matmul", "cholesky", "cholesky_solve", "eigh"]

@@ -355,6 +355,9 @@ for _s, _t, _R in (("32", _F, VectorInteropResult32), ("64", _D, VectorInteropRe
     if hasattr(lib, _m + "cholesky" + _s):  # (as above)
         _proto(_m + "cholesky" + _s, C.c_int32, _P, _D, C.POINTER(_P))
         _proto(_m + "cholesky_solve" + _s, C.c_int32, _P, _P, C.c_int32, C.POINTER(_P))
+    # the eigendecomposition of a Hermitian matrix (linalg.eigh)
+    if hasattr(lib, _m + "eigh" + _s):  # (as above)
+        _proto(_m + "eigh" + _s, C.c_int32, _P, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int32))
 
 WINDOW_FN32 = C.CFUNCTYPE(_F, _P, _SZ, _SZ)
 WINDOW_FN64 = C.CFUNCTYPE(_D, _P, _SZ, _SZ)

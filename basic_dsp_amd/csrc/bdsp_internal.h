@@ -357,6 +357,17 @@ int la_cholesky(const T* a, T* out, size_t N, bool is_complex, T loading, T* scr
 template <typename T>
 int la_cholesky_solve(const T* l, const T* b, T* x, size_t N, size_t P, bool is_complex, int part, T* scratch, hipStream_t s);
 
+// mat_eigh.hip -- w (N scalars, ascending) and v (N x N, row k the k-th eigenvector conjugate-transposed) of the Hermitian
+// matrix a (only a's lower triangle and the real part of its diagonal are read).  scratch: je_scratch(N) elements; thr: one
+// device scalar; counts: je_count_words(N) device words; host_counts: as many host words.  *sweeps: the sweeps taken, or
+// JE_STATUS_NOT_FINITE / JE_STATUS_NOT_CONVERGED (mat_eigh_core.h), after which w and v hold nothing.  Synchronises: once on
+// the small path, once per outer sweep on the blocked one
+size_t je_scratch(size_t N);
+size_t je_count_words(size_t N);
+template <typename T>
+int je_eigh(const T* a, T* w, T* v, size_t N, bool is_complex, T* scratch, T* thr, unsigned* counts, unsigned* host_counts,
+            unsigned* sweeps, hipStream_t s);
+
 // bluestein.hip
 template <typename T> int bs_chirp(T* c, size_t n, bool inverse, hipStream_t s);
 template <typename T> int bs_kernel(const T* c, T* b, size_t n, size_t m, hipStream_t s);

@@ -18,6 +18,7 @@
 
 #include "bdsp_internal.h"
 #include "mat_chol_core.h"
+#include "mat_eigh_core.h"
 #include "mat_frame_core.h"
 #include "zoom_fft_core.h"
 
@@ -2174,6 +2175,62 @@ int mat_cholesky_solve(const DevMat<T>* l, const DevMat<T>* b, int part, DevMat<
     return BDSP_OK;
 }
 
+// The eigendecomposition of a Hermitian matrix (mat_eigh.hip).  Nothing of it is in the reference.  A poisoned operand
+// comes first (two poisoned results, -1), then the shape (7).  8 and no matrices when the Frobenius norm of the matrix as
+// read is not finite or the iteration has not converged after JE_MAX_SWEEPS sweeps.  The small path reads one status word
+// back after its launch, the blocked path its counts once per outer sweep: the call's only synchronisations.
+template <typename T>
+int mat_eigh(const DevMat<T>* a, DevMat<T>** wout, DevMat<T>** vout, int32_t* sweeps)
+{
+    *wout = nullptr;
+    *vout = nullptr;
+    if (sweeps) *sweeps = 0;
+    if (a->v.erroneous()) {
+        DevMat<T>*w = nullptr, *v = nullptr;
+        const int cw = la_poisoned_result<T>(a, 1, &w);
+        std::unique_ptr<DevMat<T>> wh(w);
+        if (cw != BDSP_ERR_POISONED) return cw;
+        const int cv = la_poisoned_result<T>(a, a->rows, &v);
+        if (cv != BDSP_ERR_POISONED) return cv;
+        w->v.complex_ = false;
+        *wout = wh.release();
+        *vout = v;
+        return BDSP_ERR_POISONED;
+    }
+    const size_t N = a->rows;
+    if (N != a->row_points()) return BDSP_ERR_ARG_LENGTH;
+    const size_t e = a->v.complex_ ? 2 : 1;
+    size_t total = 0, temp = 0;
+    if (!mat_extent(N, N, 0, e, &total) || !mat_extent(je_scratch(N), e, 0, 1, &temp)) return BDSP_ERR_UNSUPPORTED;
+    std::unique_ptr<DevMat<T>> w(new DevMat<T>()), v(new DevMat<T>());
+    meta_copy<T>(&w->v, &a->v);
+    w->v.complex_ = false;
+    w->rows = N ? 1 : 0;
+    BDSP_TRY(w->v.reserve(N ? N : 1));
+    w->v.valid_len = N;
+    meta_copy<T>(&v->v, &a->v);
+    v->rows = N;
+    BDSP_TRY(v->v.reserve(total ? total : 1));
+    v->v.valid_len = total;
+    unsigned taken = 1;
+    if (N) {
+        hipStream_t s = lib_stream();
+        WsBlock ws, thr, counts;
+        const size_t words = je_count_words(N);
+        if (temp) BDSP_TRY(ws.alloc(sizeof(T) * temp, s));
+        BDSP_TRY(thr.alloc(sizeof(T), s));
+        BDSP_TRY(counts.alloc(sizeof(unsigned) * words, s));
+        std::vector<unsigned> host(words, 0u);
+        BDSP_TRY(je_eigh<T>(a->v.data, w->v.data, v->v.data, N, a->v.complex_, ws.as<T>(), thr.as<T>(), counts.as<unsigned>(),
+                            host.data(), &taken, s));
+        if (taken == JE_STATUS_NOT_FINITE || taken == JE_STATUS_NOT_CONVERGED) return BDSP_ERR_CONJ_SYMMETRIC; // 8
+    }
+    if (sweeps) *sweeps = (int32_t)taken;
+    *wout = w.release();
+    *vout = v.release();
+    return BDSP_OK;
+}
+
 // row c, point j = x[j * channels + c]: the transpose of the vector seen as [points / channels][channels]
 template <typename T>
 int mat_from_interleaved(const DevVec<T>* v, size_t channels, DevMat<T>** out)
@@ -3647,6 +3704,16 @@ BDSP_MAT_MATMUL(64, double, MatBuf64)
 BDSP_MAT_CHOL(32, float, MatBuf32)
 BDSP_MAT_CHOL(64, double, MatBuf64)
 #undef BDSP_MAT_CHOL
+
+// the eigendecomposition of a Hermitian matrix (mat_eigh above)
+#define BDSP_MAT_EIGH(SFX, T, MB)                                                                           \
+    int32_t bdsp_hip_mat_eigh##SFX(const MB* a, MB** w, MB** v, int32_t* sweeps)                            \
+    { DevMat<T>*mw = nullptr, *mv = nullptr; const int c = mat_eigh<T>(MC##SFX(a), &mw, &mv, sweeps);       \
+      *w = reinterpret_cast<MB*>(mw); *v = reinterpret_cast<MB*>(mv); return c; }
+
+BDSP_MAT_EIGH(32, float, MatBuf32)
+BDSP_MAT_EIGH(64, double, MatBuf64)
+#undef BDSP_MAT_EIGH
 
 // chirp-z transform of a frequency band (op_zoom_fft above): a vector is a matrix of one row
 #define BDSP_ZOOM_FFT(SFX, T, MB, VB)                                                                       \

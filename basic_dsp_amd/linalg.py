@@ -1,5 +1,5 @@
-"""Dense linear algebra across the rows of DspMat: the matrix product, the Cholesky factorisation and the solves with its
-factor.  Module-level functions, like zoom_fft: DspVec and DspMat gain no method."""
+"""Dense linear algebra across the rows of DspMat: the matrix product, the Cholesky factorisation, the solves with its
+factor and the Hermitian eigendecomposition.  Module-level functions, like zoom_fft: DspVec and DspMat gain no method."""
 import ctypes as C
 
 from . import _lib
@@ -102,3 +102,41 @@ def cholesky_solve(l, b, part="both"):
     code = _lib.check(getattr(lib, "bdsp_hip_mat_cholesky_solve" + l._sfx)(l._h, b._h, _PARTS[part], C.byref(out)),
                       "mat_cholesky_solve" + l._sfx)
     return code, (DspMat(_handle=out.value, _sfx=l._sfx) if out.value else None)
+
+
+def eigh(a, return_sweeps=False):
+    """(code, w, v) or, with return_sweeps, (code, w, v, sweeps): the eigendecomposition of a Hermitian DspMat on the
+    device.
+
+    a is N x N points, real (symmetric) or complex (Hermitian), f32 or f64.  Only the lower triangle is read, and of the
+    diagonal only the real part: the upper triangle and the diagonal's imaginary parts may hold anything, NaN included,
+    and do not change a bit of the result.  a stays untouched.  w is a new real DspMat of 1 row x N points: the
+    eigenvalues in ascending order, ties in the order of the index a value had before sorting.  v is a new N x N DspMat of
+    a's number kind; both take domain and delta from a.  Row k of v is the k-th eigenvector conjugate-transposed:
+    v a v^H = diag(w) and v v^H = I, so matmul(v, x) is the KLT / the principal components of the rows of x, and a
+    subspace is a set of rows.  The phase of a row is arbitrary but reproducible.  sweeps counts the sweeps taken, the
+    last one, which rotated nothing, included: 1 for the identity, a diagonal matrix and the zero matrix, whose v is a
+    permutation matrix to the bit.
+
+    Codes: 0; -1 for a poisoned operand (w and v are poisoned too); 7 unless a.rows() == a.row_points() (w and v are
+    None); 8 when the Frobenius norm of the matrix as read is not finite -- a NaN or an infinity in what is read, or
+    squares that overflow -- or when the iteration has not converged after 30 sweeps (w and v are None; sweeps is 0).
+    N == 0 gives 0 and two empty matrices.  A failed allocation raises BackendError.  TypeError for anything that is not a
+    DspMat.
+
+    Method: cyclic two-sided Jacobi in the round-robin ordering; a pair (p, q) is rotated iff |a_pq| > eps |a|_F / N.  In
+    Frobenius norms |a - v^H diag(w) v| <= c_res(N, sweeps) eps |a| and |v v^H - I| <= c_orth(N, sweeps) eps with
+    c_orth = 2 K sweeps sqrt(N), c_res = 2 K sweeps (1 + sqrt(N)) + 1; K = rho N for N <= 64, else 8 (128 rho + 132)
+    times the block steps of a sweep; rho = 24 (real), 40 (complex).
+
+    Deterministic: the path, the ordering and the order of operations depend on (N, number kind, precision) only, never
+    on the device's CU count or on timing; the same call gives the same bits on every run.  One launch and one 4-byte
+    read-back for N <= 64; else blocks of 32 columns, 3 launches per block step and one small read-back per sweep.
+    Allocates its results, so it cannot be captured into a Graph."""
+    if not isinstance(a, DspMat):
+        raise TypeError("eigh: a DspMat")
+    w, v, sweeps = C.c_void_p(), C.c_void_p(), C.c_int32(0)
+    code = _lib.check(getattr(lib, "bdsp_hip_mat_eigh" + a._sfx)(a._h, C.byref(w), C.byref(v), C.byref(sweeps)), "mat_eigh" + a._sfx)
+    wm = DspMat(_handle=w.value, _sfx=a._sfx) if w.value else None
+    vm = DspMat(_handle=v.value, _sfx=a._sfx) if v.value else None
+    return (code, wm, vm, int(sweeps.value)) if return_sweeps else (code, wm, vm)

@@ -1020,6 +1020,33 @@ int32_t bdsp_hip_mat_matmul32(const MatBuf32 *a, const MatBuf32 *b, int32_t b_co
  * |b - L L^H x| <= 3 c(N) eps |L| |L|^H |x| (both). */
 int32_t bdsp_hip_mat_cholesky32(const MatBuf32 *a, double loading, MatBuf32 **out);
 int32_t bdsp_hip_mat_cholesky_solve32(const MatBuf32 *l, const MatBuf32 *b, int32_t part, MatBuf32 **out);
+/* eigh: the eigendecomposition of a Hermitian matrix on the device (nothing of it is in the reference).  a is N x N,
+ * real (symmetric) or complex (Hermitian).  Only the lower triangle is read, and of the diagonal only the real part; the
+ * upper triangle and the diagonal's imaginary parts may hold anything, NaN included; a stays untouched.  *w is a new real
+ * matrix of 1 row x N points, the eigenvalues in ascending order, ties in the order of the index a value had before
+ * sorting; *v a new N x N matrix of a's number kind; both take domain and delta from a.  Row k of v is the k-th
+ * eigenvector conjugate-transposed: v a v^H = diag(w) and v v^H = I, so matmul(v, x) is the transform to the principal
+ * components of the rows of x and a subspace is a set of rows.  The phase of a row is arbitrary but reproducible.
+ * *sweeps (sweeps may be NULL) is the number of sweeps taken, the last one, which rotated nothing, included: 1 for the
+ * identity, a diagonal matrix and the zero matrix, whose v is a permutation matrix to the bit.
+ * Codes: 0; -1 for a poisoned a, with poisoned results in *w and *v; else 7 unless a's rows equal its row points, *w =
+ * *v = NULL; 8 when the Frobenius norm of the matrix as read is not finite (a NaN or an infinity in what is read, or
+ * squares that overflow) or when the iteration has not converged after 30 sweeps, *w = *v = NULL.  N == 0 gives 0 and two
+ * empty matrices.  A failed allocation (BDSP_ERR_HIP) or a size too long for the address space (BDSP_ERR_UNSUPPORTED)
+ * returns that backend code with *w = *v = NULL.  The call allocates its results (to be deleted with
+ * bdsp_hip_mat_delete), so it cannot be captured into a graph.
+ * Method: cyclic two-sided Jacobi in the round-robin ordering; a pair (p, q) is rotated iff |a_pq| > eps |a|_F / N, by
+ * the small angle; every product-sum is one fma, a complex product four real ones, divisions and square roots correctly
+ * rounded.  N <= 64: one launch of one workgroup with the matrix in LDS, then one 4-byte read-back, the call's only
+ * synchronisation.  Larger N: blocks of 32 columns in the same ordering; 3 launches per block step (the pivot problem
+ * of a block pair, its rows, its columns), so 3 B launches per sweep with B = ceil(N / 32) (3 (B - 1) for even B), plus 3
+ * for the whole call; the call synchronises once per sweep on one small read-back of the rotation counts.  No atomics.
+ * Deterministic: the path, the ordering and the order of operations are a function of (N, number kind, precision) only,
+ * never of the device's CU count or of timing: the same call gives the same bits on every run.  In Frobenius norms, with
+ * S = *sweeps: |a - v^H diag(w) v| <= c_res(N, S) eps |a| and |v v^H - I| <= c_orth(N, S) eps, c_orth = 2 K S sqrt(N),
+ * c_res = 2 K S (1 + sqrt(N)) + 1, K = rho N for N <= 64 and 8 (128 rho + 132) times the block steps of a sweep above,
+ * rho = 24 (real), 40 (complex). */
+int32_t bdsp_hip_mat_eigh32(const MatBuf32 *a, MatBuf32 **w, MatBuf32 **v, int32_t *sweeps);
 
 MatBuf64 *bdsp_hip_mat_new64(int32_t is_complex, int32_t domain, size_t rows, size_t row_len, double delta); /* row_len in scalars; zero filled */
 void bdsp_hip_mat_delete64(MatBuf64 *m);
@@ -1198,6 +1225,8 @@ int32_t bdsp_hip_mat_matmul64(const MatBuf64 *a, const MatBuf64 *b, int32_t b_co
 /* Hermitian positive-definite systems: see bdsp_hip_mat_cholesky32 */
 int32_t bdsp_hip_mat_cholesky64(const MatBuf64 *a, double loading, MatBuf64 **out);
 int32_t bdsp_hip_mat_cholesky_solve64(const MatBuf64 *l, const MatBuf64 *b, int32_t part, MatBuf64 **out);
+/* the eigendecomposition of a Hermitian matrix: see bdsp_hip_mat_eigh32 */
+int32_t bdsp_hip_mat_eigh64(const MatBuf64 *a, MatBuf64 **w, MatBuf64 **v, int32_t *sweeps);
 
 /* ==========================================================================================
  * B3 -- kernels on caller-owned DEVICE memory.  `stream` is a hipStream_t passed as void*
