@@ -9,6 +9,7 @@ from .vector import DspVec  # noqa: F401
 from .matrix import DspMat  # noqa: F401
 from .spectral import zoom_fft  # noqa: F401
 from .linalg import matmul, cholesky, cholesky_solve, eigh  # noqa: F401
+from .iir import sosfilt  # noqa: F401
 
 __all__ = ["DspVec", "DspMat", "Graph", "BackendError", "lib", "LIB_PATH", "last_error", "require_gpu", "zoom_fft",
-           "matmul", "cholesky", "cholesky_solve", "eigh"]
+           "matmul", "cholesky", "cholesky_solve", "eigh", "sosfilt"]

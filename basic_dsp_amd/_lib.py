@@ -358,6 +358,10 @@ for _s, _t, _R in (("32", _F, VectorInteropResult32), ("64", _D, VectorInteropRe
     # the eigendecomposition of a Hermitian matrix (linalg.eigh)
     if hasattr(lib, _m + "eigh" + _s):  # (as above)
         _proto(_m + "eigh" + _s, C.c_int32, _P, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int32))
+    # second-order-section (IIR) filtering along the rows (iir.sosfilt): the coefficients are doubles in both precisions
+    if hasattr(lib, "bdsp_hip_sosfilt" + _s):  # (as above)
+        _proto("bdsp_hip_sosfilt" + _s, C.c_int32, _P, C.POINTER(_D), _SZ, _P)
+        _proto(_m + "sosfilt" + _s, C.c_int32, _P, C.POINTER(_D), _SZ, _P)
 
 WINDOW_FN32 = C.CFUNCTYPE(_F, _P, _SZ, _SZ)
 WINDOW_FN64 = C.CFUNCTYPE(_D, _P, _SZ, _SZ)

@@ -379,6 +379,15 @@ template <typename T>
 int bs_post(const T* conv, T* out, const T* c, size_t n, size_t m, size_t batch, int out_kind, size_t rot,
             int div_window_id, T alpha, hipStream_t s);
 
+// iir.hip -- S second-order sections along every row of rows x n points, in place (iir_core.h); tab, m (the cascade's
+// transition over one tile) and carry (iir_carry_doubles doubles) are device buffers, m and carry only for rows longer than
+// a tile; state (may be null): rows x 2S points, read and overwritten.  One launch or three, whatever the row count
+template <typename T> struct IirSec;
+size_t iir_carry_doubles(size_t rows, size_t n, bool is_complex, size_t S);
+template <typename T>
+int iir_sosfilt(T* data, size_t rows, size_t n, bool is_complex, const IirSec<T>* tab, size_t S, T* state, const double* m,
+                double* carry, hipStream_t s);
+
 // zoom_fft.hip -- chirp-z transform of a band: rows x n points -> rows x bins complex, l = zf_conv_len(n, bins)
 // (zoom_fft_core.h); the launch counts do not depend on `rows`
 // the three tables of a plan: pre (n), post (bins) and the wrapped kernel (l, not yet transformed); start reduced modulo

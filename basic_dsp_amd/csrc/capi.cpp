@@ -19,6 +19,7 @@
 #include "bdsp_internal.h"
 #include "mat_chol_core.h"
 #include "mat_eigh_core.h"
+#include "iir_core.h"
 #include "mat_frame_core.h"
 #include "zoom_fft_core.h"
 
@@ -2231,6 +2232,47 @@ int mat_eigh(const DevMat<T>* a, DevMat<T>** wout, DevMat<T>** vout, int32_t* sw
     return BDSP_OK;
 }
 
+// sosfilt (iir.hip): S second-order sections, direct form II transposed, along every row of a time-domain vector or matrix
+// (a vector is one row), in place; complex rows as two real signals.  Nothing of it is in the reference.  sos: S rows
+// b0 b1 b2 a0 a1 a2, divided by a0 in double and rounded once to T.  state (may be null): rows x 2S points of the data's
+// number kind, s1 s2 per section, read as the initial state and overwritten with the final one.  An argument error of the
+// coefficients comes first (7, the data untouched), then a poisoned operand (the callers answer -1), the domain (5), the
+// state's number kind (2) and its shape (7).  One launch for rows of one tile, else three, whatever the row count.  The
+// call uploads its tables, so it cannot be captured into a HIP graph.
+template <typename T>
+int op_sosfilt(DevVec<T>* v, size_t rows, const double* sos, size_t S, DevVec<T>* state, size_t state_rows)
+{
+    if (S > (size_t)IIR_MAX_SECTIONS || (S > 0 && !sos) || !iir_sos_valid(sos, S)) return BDSP_ERR_ARG_LENGTH;
+    if (v->erroneous()) return BDSP_OK;
+    if (state && state->erroneous()) return BDSP_ERR_POISONED;
+    if (v->freq) return BDSP_ERR_MUST_BE_TIME;
+    if (state) {
+        if (state->complex_ != v->complex_) return BDSP_ERR_META_DATA;
+        if (state_rows != rows || (rows > 0 && state->points() != rows * 2 * S)) return BDSP_ERR_ARG_LENGTH;
+    }
+    if (S == 0 || rows == 0) return BDSP_OK;
+    const size_t n = v->points() / rows;
+    if (n == 0) return BDSP_OK;
+    hipStream_t s = lib_stream();
+    std::vector<IirSec<T>> tab(S);
+    const bool carried = iir_launches(n) == 3;
+    std::vector<double> m(carried ? 4 * S * S : 0);
+    iir_make_tables<T>(sos, S, tab.data(), carried ? m.data() : nullptr);
+    size_t carry = 0;
+    if (!mat_extent(iir_carry_doubles(rows, n, v->complex_, S), 1, 0, 1, &carry)) return BDSP_ERR_UNSUPPORTED;
+    WsBlock wt, wm, wc;
+    BDSP_TRY(wt.alloc(sizeof(IirSec<T>) * S, s));
+    // (pageable memory: the copies have left `tab` and `m` when the calls return)
+    BDSP_HIP_TRY(hipMemcpyAsync(wt.p, tab.data(), sizeof(IirSec<T>) * S, hipMemcpyHostToDevice, s));
+    if (carried) {
+        BDSP_TRY(wm.alloc(sizeof(double) * m.size(), s));
+        BDSP_HIP_TRY(hipMemcpyAsync(wm.p, m.data(), sizeof(double) * m.size(), hipMemcpyHostToDevice, s));
+        BDSP_TRY(wc.alloc(sizeof(double) * carry, s));
+    }
+    return iir_sosfilt<T>(v->data, rows, n, v->complex_, wt.as<IirSec<T>>(), S, state ? state->data : nullptr, wm.as<double>(),
+                          wc.as<double>(), s);
+}
+
 // row c, point j = x[j * channels + c]: the transpose of the vector seen as [points / channels][channels]
 template <typename T>
 int mat_from_interleaved(const DevVec<T>* v, size_t channels, DevMat<T>** out)
@@ -3727,6 +3769,18 @@ BDSP_MAT_EIGH(64, double, MatBuf64)
 BDSP_ZOOM_FFT(32, float, MatBuf32, VecBuf32)
 BDSP_ZOOM_FFT(64, double, MatBuf64, VecBuf64)
 #undef BDSP_ZOOM_FFT
+
+// second-order-section filtering along the rows (op_sosfilt above): a vector is a matrix of one row
+#define BDSP_SOSFILT(SFX, T, MB, VB)                                                                        \
+    int32_t bdsp_hip_sosfilt##SFX(VB* vector, const double* sos, size_t sections, VB* state)                \
+    { DevVec<T>* v = H<T>(vector); return finish<T>(v, op_sosfilt<T>(v, 1, sos, sections, state ? H<T>(state) : nullptr, 1)).result_code; } \
+    int32_t bdsp_hip_mat_sosfilt##SFX(MB* m, const double* sos, size_t sections, MB* state)                 \
+    { DevMat<T>* a = M##SFX(m); DevMat<T>* st = state ? M##SFX(state) : nullptr;                            \
+      return mat_code<T>(a, op_sosfilt<T>(&a->v, a->rows, sos, sections, st ? &st->v : nullptr, st ? st->rows : 0)); }
+
+BDSP_SOSFILT(32, float, MatBuf32, VecBuf32)
+BDSP_SOSFILT(64, double, MatBuf64, VecBuf64)
+#undef BDSP_SOSFILT
 
 // ---------------------------------------------------------------------------------------------- B3
 int bdsp_hip_dev_fft(int elem, void* data, void* scratch, size_t points, size_t batch, unsigned flags,

@@ -1047,6 +1047,31 @@ int32_t bdsp_hip_mat_cholesky_solve32(const MatBuf32 *l, const MatBuf32 *b, int3
  * c_res = 2 K S (1 + sqrt(N)) + 1, K = rho N for N <= 64 and 8 (128 rho + 132) times the block steps of a sweep above,
  * rho = 24 (real), 40 (complex). */
 int32_t bdsp_hip_mat_eigh32(const MatBuf32 *a, MatBuf32 **w, MatBuf32 **v, int32_t *sweeps);
+/* sosfilt: recursive (IIR) filtering with a cascade of second-order sections along a vector or along every row of a
+ * matrix, in place (nothing of it is in the reference).  sos holds `sections` rows of six doubles b0 b1 b2 a0 a1 a2, the
+ * layout of scipy's output='sos'; every section is divided by its a0 in double and rounded once to the data's precision.
+ * A section is direct form II transposed, y = b0 x + s1, s1 <- b1 x - a1 y + s2, s2 <- b2 x - a2 y, the form and state
+ * convention of scipy.signal.sosfilt; the sections are applied in order.  The data are real or complex in the time domain;
+ * complex data are filtered as two independent real signals (the coefficients are real).  Length, domain, delta and
+ * number kind stay.  state (may be NULL: zero initial state, the final state is dropped) is a vector of 2 * sections
+ * points, for a matrix a matrix of rows x 2 * sections points, of the data's number kind: s1, s2 of section 0, then of
+ * section 1, ...; it is read as the initial state and overwritten with the state after the last point, so a recording can
+ * be filtered block after block.
+ * Codes: 0; 7, with the data untouched, for sections > 0 with a NULL sos, a coefficient that is not finite, a0 == 0,
+ * sections above 16 (IIR_MAX_SECTIONS) or a state of the wrong shape; -1 for a poisoned vector, matrix or state; 5 for
+ * frequency-domain data; 2 for a state of the other number kind.  sections == 0, no rows, or rows of no points: 0 and
+ * nothing changes.  An unstable filter gives inf or NaN as the recurrence would, with code 0: nothing is tested.  A failed
+ * allocation (BDSP_ERR_HIP) or rows x tiles above 2^31 (BDSP_ERR_UNSUPPORTED) returns that backend code.  The call
+ * uploads its coefficient tables, so it cannot be captured into a graph.
+ * Method: a row is cut into tiles of 4096 points, a tile into 256 chunks of 16; every lane runs its chunk from a zero
+ * state, the chunk end states are combined by a fixed tree of the maps s -> A^16 s + e with host tables A^(16 * 2^k), and
+ * every lane runs its chunk again from its true state.  Rows of one tile: one launch.  Longer rows: three launches (end
+ * states of the tiles from zero, the carry along the row in double, the tiles from their true states), whatever the row
+ * count.  No atomics, no workgroup waits for another.  Deterministic: the result is a function of (row length, sos,
+ * number kind, precision, incoming state) only, never of the row count, the device's CU count or of timing: row r of the
+ * matrix call is bit-equal to the vector call on that row. */
+int32_t bdsp_hip_sosfilt32(VecBuf32 *v, const double *sos, size_t sections, VecBuf32 *state /* may be NULL */);
+int32_t bdsp_hip_mat_sosfilt32(MatBuf32 *m, const double *sos, size_t sections, MatBuf32 *state /* may be NULL */);
 
 MatBuf64 *bdsp_hip_mat_new64(int32_t is_complex, int32_t domain, size_t rows, size_t row_len, double delta); /* row_len in scalars; zero filled */
 void bdsp_hip_mat_delete64(MatBuf64 *m);
@@ -1227,6 +1252,9 @@ int32_t bdsp_hip_mat_cholesky64(const MatBuf64 *a, double loading, MatBuf64 **ou
 int32_t bdsp_hip_mat_cholesky_solve64(const MatBuf64 *l, const MatBuf64 *b, int32_t part, MatBuf64 **out);
 /* the eigendecomposition of a Hermitian matrix: see bdsp_hip_mat_eigh32 */
 int32_t bdsp_hip_mat_eigh64(const MatBuf64 *a, MatBuf64 **w, MatBuf64 **v, int32_t *sweeps);
+/* second-order-section filtering: see bdsp_hip_sosfilt32 */
+int32_t bdsp_hip_sosfilt64(VecBuf64 *v, const double *sos, size_t sections, VecBuf64 *state /* may be NULL */);
+int32_t bdsp_hip_mat_sosfilt64(MatBuf64 *m, const double *sos, size_t sections, MatBuf64 *state /* may be NULL */);
 
 /* ==========================================================================================
  * B3 -- kernels on caller-owned DEVICE memory.  `stream` is a hipStream_t passed as void*
