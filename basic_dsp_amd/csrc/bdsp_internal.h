@@ -75,6 +75,14 @@ __device__ __forceinline__ C nt_load(const C* p)
 
 int num_cus();
 
+// Launch attributes of a kernel on the CURRENT device (runtime.cpp).  kernel_lds: call before every launch with `bytes` of
+// dynamic LDS; raises the kernel's limit where bytes > 64 KiB.  kernel_slots: the same, and *per_cu = the resident workgroups
+// per CU as the runtime computes them (at least 1), asked once per (device, kernel, threads, lds) -- for persistent grids.
+int kernel_lds(const void* kernel, size_t bytes);
+int kernel_slots(const void* kernel, int threads, size_t lds, int* per_cu);
+template <typename K> int kernel_lds(K* kernel, size_t bytes) { return kernel_lds(reinterpret_cast<const void*>(kernel), bytes); }
+template <typename K> int kernel_slots(K* kernel, int threads, size_t lds, int* per_cu) { return kernel_slots(reinterpret_cast<const void*>(kernel), threads, lds, per_cu); }
+
 struct WsBlock { // RAII workspace
     void* p = nullptr;
     hipStream_t s = nullptr;

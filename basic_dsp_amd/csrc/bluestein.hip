@@ -199,8 +199,7 @@ static int launch_bs_wg(const T* x, T* y, const T* c, const T* bspec, size_t n, 
     using F = WgFft<T, M, M / 16>;
     const size_t lds = ((size_t)B * (F::LDS_ELEMS + 1) + 16 * 17) * sizeof(cpx<T>);
     auto k = k_bluestein_wg<T, M>;
-    if (lds > 64 * 1024)
-        BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    BDSP_TRY(kernel_lds(k, lds));
     size_t groups = (batch + B - 1) / B, slots = (size_t)num_cus() * 4;
     hipLaunchKernelGGL(k, dim3((unsigned)(groups < slots ? groups : slots)), dim3(256), lds, s, reinterpret_cast<const cpx<T>*>(x),
                        reinterpret_cast<cpx<T>*>(y), reinterpret_cast<const cpx<T>*>(c),

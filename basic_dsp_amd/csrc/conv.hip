@@ -407,9 +407,7 @@ int conv_run_blocks(const T* in, T* out, size_t points, size_t batch, const T* h
     size_t lds = conv_lds_bytes<T>();
     constexpr bool FAST = sizeof(T) == 4;
     auto kern = real_data ? k_overlap_save<T, FAST, true> : k_overlap_save<T, FAST, false>;
-    if (lds > 64 * 1024)
-        BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    BDSP_TRY(kernel_lds(kern, lds));
     // persistent-ish grid: enough workgroups to fill every CU at the occupancy LDS/VGPRs allow,
     // each walking blocks with a grid stride so the register-resident twiddles are loaded once
     int per_cu = sizeof(T) == 4 ? 3 : 2;

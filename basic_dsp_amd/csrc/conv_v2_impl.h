@@ -294,22 +294,22 @@ static int launch_v2(const ConvV2Args<T>& a, unsigned grid, size_t lds, hipStrea
     // streamed results: complex data only, through the batched instantiation (it serves single vectors too)
     if (!real && nts) {
         auto kern = k_overlap_save_v2<T, R0, true, false, true>;
-        if (lds > 64 * 1024) BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        BDSP_TRY(kernel_lds(kern, lds));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a);
         BDSP_LAUNCH_CHECK();
         return BDSP_OK;
     }
     if (real) {
         auto kern = k_overlap_save_v2<T, R0, true, true>; // (the batched instantiation serves single vectors too)
-        if (lds > 64 * 1024) BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        BDSP_TRY(kernel_lds(kern, lds));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a);
     } else if (a.batch > 1) {
         auto kern = k_overlap_save_v2<T, R0, true>;
-        if (lds > 64 * 1024) BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        BDSP_TRY(kernel_lds(kern, lds));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a);
     } else {
         auto kern = k_overlap_save_v2<T, R0, false>;
-        if (lds > 64 * 1024) BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        BDSP_TRY(kernel_lds(kern, lds));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a);
     }
     BDSP_LAUNCH_CHECK();

@@ -659,15 +659,6 @@ static size_t wg_lds_bytes(int n)
     return (size_t)b * col_stride(n) * sizeof(cpx<T>);
 }
 
-template <typename K>
-static int set_lds(K kernel, size_t bytes)
-{
-    if (bytes > 64 * 1024)
-        BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return BDSP_OK;
-}
-
 template <typename T, int N>
 static int launch_wg4(const FftIo<T>& io, size_t batch, bool inverse, hipStream_t s)
 {
@@ -678,10 +669,10 @@ static int launch_wg4(const FftIo<T>& io, size_t batch, bool inverse, hipStream_
     const size_t slots = (size_t)num_cus() * (N == 8192 ? 2 : 1);
     const unsigned grid = (unsigned)(batch < slots ? batch : slots);
     if (inverse) {
-        BDSP_TRY(set_lds(k_fft_wg4<T, N, 1>, lds));
+        BDSP_TRY(kernel_lds(k_fft_wg4<T, N, 1>, lds));
         hipLaunchKernelGGL((k_fft_wg4<T, N, 1>), dim3(grid), dim3(N / 16), lds, s, io, wtab, batch);
     } else {
-        BDSP_TRY(set_lds(k_fft_wg4<T, N, -1>, lds));
+        BDSP_TRY(kernel_lds(k_fft_wg4<T, N, -1>, lds));
         hipLaunchKernelGGL((k_fft_wg4<T, N, -1>), dim3(grid), dim3(N / 16), lds, s, io, wtab, batch);
     }
     BDSP_LAUNCH_CHECK();
@@ -708,22 +699,17 @@ static int launch_wg(const FftIo<T>& io, size_t batch, bool inverse, hipStream_t
 #endif
     if constexpr (WGBATCH && BDSP_FFT_PART != 2) {
         // enough transforms to keep persistent workgroups busy for several rounds
-        // resident workgroups per CU as the runtime computes it (registers and LDS), once per kernel
+        // resident workgroups per CU as the runtime computes it (registers and LDS); the forward kernel's for both directions
         size_t lds2 = lds + 16 * 17 * sizeof(cpx<T>);
-        static int occ = 0;
-        if (occ == 0) {
-            int o = 0;
-            (void)set_lds(k_fft_wg_batch<T, N, -1>, lds2);
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k_fft_wg_batch<T, N, -1>, 256, lds2) != hipSuccess || o < 1) o = 1;
-            occ = o;
-        }
+        int occ = 1;
+        if (kernel_slots(k_fft_wg_batch<T, N, -1>, 256, lds2, &occ) != BDSP_OK) occ = 1; // (the launch taken reports)
         const size_t slots = (size_t)num_cus() * (size_t)occ;
         if (!gen && grid >= 4 * slots && !(io.flags & (BDSP_FFT_MAGNITUDE | FFT_OUT_REAL | FFT_IN_REAL))) {
             if (inverse) {
-                BDSP_TRY(set_lds(k_fft_wg_batch<T, N, 1>, lds2));
+                BDSP_TRY(kernel_lds(k_fft_wg_batch<T, N, 1>, lds2));
                 hipLaunchKernelGGL((k_fft_wg_batch<T, N, 1>), dim3((unsigned)slots), dim3(256), lds2, s, io, wtab, batch);
             } else {
-                BDSP_TRY(set_lds(k_fft_wg_batch<T, N, -1>, lds2));
+                BDSP_TRY(kernel_lds(k_fft_wg_batch<T, N, -1>, lds2));
                 hipLaunchKernelGGL((k_fft_wg_batch<T, N, -1>), dim3((unsigned)slots), dim3(256), lds2, s, io, wtab, batch);
             }
             BDSP_LAUNCH_CHECK();
@@ -732,7 +718,7 @@ static int launch_wg(const FftIo<T>& io, size_t batch, bool inverse, hipStream_t
     }
 #define BDSP_WG(DIRV, GENV)                                                                        \
     do {                                                                                           \
-        BDSP_TRY(set_lds(k_fft_wg<T, N, DIRV, GENV>, lds));                                        \
+        BDSP_TRY(kernel_lds(k_fft_wg<T, N, DIRV, GENV>, lds));                                     \
         hipLaunchKernelGGL((k_fft_wg<T, N, DIRV, GENV>), dim3(grid), dim3(256), lds, s, io, wtab,  \
                            batch);                                                                 \
     } while (0)
@@ -813,7 +799,7 @@ static int launch_pass(const FftPassRoute& r, const FftIo<T>& io_in, const cpx<T
         constexpr size_t lds = pass_tile_lds_bytes<T, RP, W, GENV>() +                             \
                                (pass_lds_twiddles<T, RP, W, GENV>() ? (size_t)RP * sizeof(cpx<T>) : 0); \
         if (lds != r.lds_bytes) { set_last_error("fft pass: route and kernel disagree on LDS"); return BDSP_ERR_UNSUPPORTED; } \
-        BDSP_TRY(set_lds(k_fft_pass<T, RP, W, DIRV, RM, GENV, SV, WINV, NTLV>, lds));              \
+        BDSP_TRY(kernel_lds(k_fft_pass<T, RP, W, DIRV, RM, GENV, SV, WINV, NTLV>, lds));           \
         hipLaunchKernelGGL((k_fft_pass<T, RP, W, DIRV, RM, GENV, SV, WINV, NTLV>), grid, dim3(THREADS), lds, s, \
                            io, src, dst, wtab, n, nsg, tiles, (int)last);                          \
     } while (0)

@@ -161,15 +161,6 @@ __global__ __launch_bounds__(IIR_WAVE) void k_iir_carry(double* buf, const T* __
     }
 }
 
-// on every launch: the attribute belongs to the current device's copy of the kernel
-template <typename Kern>
-static int iir_allow_lds(Kern kern, size_t lds)
-{
-    if (lds > 64 * 1024)
-        BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return BDSP_OK;
-}
-
 size_t iir_carry_doubles(size_t rows, size_t n, bool is_complex, size_t S)
 {
     return iir_launches(n) < 3 ? 0 : rows * iir_tiles(n) * (is_complex ? 2 : 1) * 2 * S;
@@ -183,21 +174,21 @@ static int iir_run(T* data, size_t rows, size_t n, const IirSec<T>* tab, size_t 
     if (rows > 0x7fffffffu / tiles) { set_last_error("sosfilt: rows x tiles above 2^31"); return BDSP_ERR_UNSUPPORTED; }
     auto kern = k_iir_tile<T, C>;
     if (iir_launches(n) == 1) {
-        BDSP_TRY(iir_allow_lds(kern, lds));
+        BDSP_TRY(kernel_lds(kern, lds));
         hipLaunchKernelGGL(kern, dim3((unsigned)rows), dim3(IIR_THREADS), lds, s, data, n, tab, (int)S, (const T*)state,
                            (const double*)nullptr, (double*)nullptr, state, 1u, 1u);
         BDSP_LAUNCH_CHECK();
         return BDSP_OK;
     }
     if (!carry || !m) return BDSP_ERR_UNSUPPORTED;
-    BDSP_TRY(iir_allow_lds(kern, lds));
+    BDSP_TRY(kernel_lds(kern, lds));
     hipLaunchKernelGGL(kern, dim3((unsigned)(rows * (tiles - 1))), dim3(IIR_THREADS), lds, s, data, n, tab, (int)S, (const T*)nullptr,
                        (const double*)nullptr, carry, (T*)nullptr, (unsigned)tiles, (unsigned)(tiles - 1));
     BDSP_LAUNCH_CHECK();
     hipLaunchKernelGGL((k_iir_carry<T>), dim3((unsigned)(rows * C)), dim3(IIR_WAVE), 0, s, carry, (const T*)state, m, (int)S, C,
                        (unsigned)tiles);
     BDSP_LAUNCH_CHECK();
-    BDSP_TRY(iir_allow_lds(kern, lds));
+    BDSP_TRY(kernel_lds(kern, lds));
     hipLaunchKernelGGL(kern, dim3((unsigned)(rows * tiles)), dim3(IIR_THREADS), lds, s, data, n, tab, (int)S, (const T*)nullptr,
                        (const double*)carry, (double*)nullptr, state, (unsigned)tiles, (unsigned)tiles);
     BDSP_LAUNCH_CHECK();

@@ -1088,8 +1088,7 @@ int interpolatef_dev(const T* in, T* out, size_t len, bool is_complex, int fid, 
 #define BDSP_INNER2(FV, CP, QV)                                                                    \
     do {                                                                                           \
         auto kk = k_interp_inner<T, CP, FV, QV>;                                                   \
-        if (lds2 > 64 * 1024)                                                                      \
-            BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2)); \
+        BDSP_TRY(kernel_lds(kk, lds2));                                                            \
         hipLaunchKernelGGL(kk, dim3(g + (unsigned)eblocks), dim3(256), lds2, s, in, out, taps_dev, q_lo, q_hi, (int)conv_len, \
                            (long long)points, (long long)new_points, g, stream_out);               \
     } while (0)
@@ -1213,8 +1212,7 @@ int mat_interpolatef_dev(const T* in, T* out, size_t rows, size_t row_len, bool 
 #define BDSP_INNER2(FV, CP, QV)                                                                    \
     do {                                                                                           \
         auto kk = k_mat_interpf_inner<T, CP, FV, QV>;                                              \
-        if (lds2 > 64 * 1024)                                                                      \
-            BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2)); \
+        BDSP_TRY(kernel_lds(kk, lds2));                                                            \
         hipLaunchKernelGGL(kk, dim3((unsigned)grid), dim3(256), lds2, s, in, out, taps_dev, q_lo, q_hi, (int)conv_len, \
                            (long long)points, (long long)new_points, g, eb, rows, tap_stride, stream_out); \
     } while (0)

@@ -319,9 +319,7 @@ static int la_launch_panel(const T* src, size_t ld_src, bool masked, T loading, 
     const size_t lds = sizeof(T) * la_panel_lds_scalars(CPLX, rows_below != 0);
     const size_t blocks = rows_below ? (rows_below + LA_BLOCK - 1) / LA_BLOCK : 1;
     auto kern = k_la_panel<T, CPLX>;
-    // on every launch: the attribute belongs to the current device's copy of the kernel
-    if (lds > 64 * 1024)
-        BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    BDSP_TRY(kernel_lds(kern, lds));
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(LA_THREADS), lds, s, src, ld_src, masked ? 1 : 0, loading, out, ld_out,
                        (int)n, rows_below, flag);
     BDSP_LAUNCH_CHECK();

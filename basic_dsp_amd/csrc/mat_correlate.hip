@@ -151,10 +151,7 @@ static int mc_launch(const T* in, T* out, const T* arg, size_t arg_stride, size_
     const size_t lds = (size_t)B * mc_col_stride(N) * sizeof(cpx<T>);
     const size_t groups = (rows + B - 1) / B;
     if (groups > 0x7fffffffu) { set_last_error("correlate: too many rows for one launch"); return BDSP_ERR_UNSUPPORTED; }
-    // on every launch: the attribute belongs to the current device's copy of the kernel
-    if (lds > 64 * 1024)
-        BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mc_correlate<T, N>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    BDSP_TRY(kernel_lds(k_mc_correlate<T, N>, lds));
     const int d0 = (int)((N - p) - (N - p) / 2);
     hipLaunchKernelGGL((k_mc_correlate<T, N>), dim3((unsigned)groups), dim3(256), lds, s,
                        reinterpret_cast<const cpx<T>*>(in), reinterpret_cast<cpx<T>*>(out),

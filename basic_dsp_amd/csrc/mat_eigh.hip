@@ -206,21 +206,12 @@ __global__ __launch_bounds__(JE_THREADS) void k_je_sorted(const T* __restrict__ 
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
-// on every launch: the attribute belongs to the current device's copy of the kernel
-template <typename K>
-static int je_allow_lds(K kern, size_t lds)
-{
-    if (lds > 64 * 1024)
-        BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return BDSP_OK;
-}
-
 template <typename T, bool CPLX>
 static int je_run_small(const T* a, T* w, T* v, size_t N, unsigned* status, hipStream_t s)
 {
     const size_t lds = sizeof(T) * je_lds_scalars(CPLX);
     auto kern = k_je_small<T, CPLX>;
-    BDSP_TRY(je_allow_lds(kern, lds));
+    BDSP_TRY(kernel_lds(kern, lds));
     hipLaunchKernelGGL(kern, dim3(1), dim3(JE_THREADS), lds, s, a, (int)N, w, v, status);
     BDSP_LAUNCH_CHECK();
     return BDSP_OK;
@@ -260,14 +251,14 @@ static int je_run_blocked(const T* a, T* w, T* v, size_t N, T* scratch, T* thr, 
     *sweeps = 0;
     for (int sweep = 1; sweep <= JE_MAX_SWEEPS; ++sweep) {
         for (int step = 0; step < steps; ++step) {
-            BDSP_TRY(je_allow_lds(pivot, lds_pivot));
+            BDSP_TRY(kernel_lds(pivot, lds_pivot));
             hipLaunchKernelGGL(pivot, dim3((unsigned)pairs), dim3(JE_THREADS), lds_pivot, s, wk, N, nb, step, (const T*)thr, jt,
                                counts + 1 + (size_t)step * pairs);
             BDSP_LAUNCH_CHECK();
-            BDSP_TRY(je_allow_lds(rows, lds_tile));
+            BDSP_TRY(kernel_lds(rows, lds_tile));
             hipLaunchKernelGGL(rows, dim3((unsigned)(pairs * 2 * nb)), dim3(JE_THREADS), lds_tile, s, wk, vw, N, nb, step, (const T*)jt);
             BDSP_LAUNCH_CHECK();
-            BDSP_TRY(je_allow_lds(cols, lds_tile));
+            BDSP_TRY(kernel_lds(cols, lds_tile));
             hipLaunchKernelGGL(cols, dim3((unsigned)(pairs * nb)), dim3(JE_THREADS), lds_tile, s, wk, N, nb, step, (const T*)jt);
             BDSP_LAUNCH_CHECK();
         }

@@ -196,7 +196,7 @@ __global__ __launch_bounds__(256) void k_mt_conv_direct(const T* __restrict__ in
 }
 
 // Staging budget: 64 KB keeps two workgroups resident on a compute unit's 160 KB and stays within what a kernel gets
-// without hipFuncSetAttribute(MaxDynamicSharedMemorySize); windows above it take the unstaged variant.
+// without a raised dynamic-LDS limit (kernel_lds); windows above it take the unstaged variant.
 constexpr size_t MT_CONV_LDS_BUDGET = 64 * 1024;
 
 template <typename T, bool CPLX, bool CW>

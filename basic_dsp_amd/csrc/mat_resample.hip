@@ -297,10 +297,7 @@ static int rs_launch(const T* in, T* out, size_t rows, size_t p, bool is_real, i
     const size_t lds = (size_t)B * rs_col_stride(N) * sizeof(cpx<T>);
     const size_t groups = (rows + B - 1) / B;
     if (groups > 0x7fffffffu) { set_last_error("resample: too many rows for one launch"); return BDSP_ERR_UNSUPPORTED; }
-    // on every launch: the attribute belongs to the current device's copy of the kernel
-    if (lds > 64 * 1024)
-        BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rs_fused<T, N>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    BDSP_TRY(kernel_lds(k_rs_fused<T, N>, lds));
     int lf = 0;
     while ((p << lf) < (size_t)N) ++lf;
     hipLaunchKernelGGL((k_rs_fused<T, N>), dim3((unsigned)groups), dim3(256), lds, s, in, out, wtab, rows, lf,

@@ -17,6 +17,7 @@
 #include "bdsp_internal.h"
 #include "dsp_funcs.h"
 #include "mr_dft.h"
+#include "mr_reg_io.h"
 #include <algorithm>
 #include <mutex>
 #include <unordered_map>
@@ -482,31 +483,6 @@ static unsigned mr_threads(size_t tile_points)
     return (unsigned)(t < 64 ? 64 : (t > (size_t)MR_THREADS ? (size_t)MR_THREADS : t));
 }
 
-template <typename K>
-static int mr_set_lds(K kern, size_t lds)
-{
-    if (lds > 64 * 1024)
-        BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return BDSP_OK;
-}
-
-// k_mr_reg3 (mixed_radix_reg3.h, instantiated in mixed_radix_reg3_f32.hip / _f64.hip): returns MR_REG3_NOT_BUILT when the
-// length has no instantiation (the caller then takes k_mr_wg)
-constexpr int MR_REG3_NOT_BUILT = 1 << 20;
-template <typename T>
-struct MrReg3Io { // (layout: mixed_radix_reg3.h)
-    const T* in;
-    T* out;
-    unsigned rot_in, rot_out;
-    T in_scale;
-    int in_real, out_kind, plain, window_id, window_div;
-    T alpha;
-};
-template <typename T>
-int mr_reg3_launch(const MrReg3Io<T>& io, size_t n, size_t batch, bool inverse, hipStream_t s);
-template <typename T>
-int mr_reg2_launch(const MrReg3Io<T>& io, size_t n, size_t batch, bool inverse, hipStream_t s); // (mixed_radix_reg2.h: n < 300)
-
 // in -> out (may alias for the workgroup-resident path; the four-step path needs `scratch` of n * batch complex)
 template <typename T>
 int mr_fft(const T* in, T* out, T* scratch, size_t n, size_t batch, bool inverse, unsigned flags, T in_scale,
@@ -551,10 +527,10 @@ int mr_fft(const T* in, T* out, T* scratch, size_t n, size_t batch, bool inverse
         // 1024 threads each
         const unsigned threads = grid >= 2u * (unsigned)num_cus() ? (mr_threads(n * lanes) > 256u ? 256u : mr_threads(n * lanes)) : mr_threads(4 * n * lanes);
         if (inverse) {
-            BDSP_TRY(mr_set_lds(k_mr_wg<T, 1>, lds));
+            BDSP_TRY(kernel_lds(k_mr_wg<T, 1>, lds));
             hipLaunchKernelGGL((k_mr_wg<T, 1>), dim3(grid), dim3(threads), lds, s, io, st, tw, (int)lanes, (unsigned long long)batch);
         } else {
-            BDSP_TRY(mr_set_lds(k_mr_wg<T, -1>, lds));
+            BDSP_TRY(kernel_lds(k_mr_wg<T, -1>, lds));
             hipLaunchKernelGGL((k_mr_wg<T, -1>), dim3(grid), dim3(threads), lds, s, io, st, tw, (int)lanes, (unsigned long long)batch);
         }
         BDSP_LAUNCH_CHECK();
@@ -584,7 +560,7 @@ int mr_fft(const T* in, T* out, T* scratch, size_t n, size_t batch, bool inverse
             const unsigned th = mr_threads(2 * RP * W);
 #define BDSP_GPASS(DIRV, POSV)                                                                                          \
     do {                                                                                                                \
-        BDSP_TRY(mr_set_lds(k_mr_gpass<T, DIRV, POSV>, lds));                                                           \
+        BDSP_TRY(kernel_lds(k_mr_gpass<T, DIRV, POSV>, lds));                                                           \
         hipLaunchKernelGGL((k_mr_gpass<T, DIRV, POSV>), g, dim3(th), lds, s, io, src, dst, sp, twp, (unsigned long long)n, (int)RP, nsg, W); \
     } while (0)
             if (inverse) { if (p == 0) BDSP_GPASS(1, 0); else if (p == 1) BDSP_GPASS(1, 1); else BDSP_GPASS(1, 2); }
@@ -615,13 +591,13 @@ int mr_fft(const T* in, T* out, T* scratch, size_t n, size_t batch, bool inverse
     const unsigned t1 = lone ? mr_threads(4 * n1 * W) : mr_threads(n1 * W), t2 = lone ? mr_threads(4 * n2 * W) : mr_threads(n2 * W);
     const dim3 g1((unsigned)((n2 + W - 1) / W), (unsigned)batch), g2((unsigned)((n1 + W - 1) / W), (unsigned)batch);
     if (inverse) {
-        BDSP_TRY(mr_set_lds(k_mr_pass1<T, 1>, lds1));
-        BDSP_TRY(mr_set_lds(k_mr_pass2<T, 1>, lds2));
+        BDSP_TRY(kernel_lds(k_mr_pass1<T, 1>, lds1));
+        BDSP_TRY(kernel_lds(k_mr_pass2<T, 1>, lds2));
         hipLaunchKernelGGL((k_mr_pass1<T, 1>), g1, dim3(t1), lds1, s, io, tmp, s1, tw1, (int)n1, (int)n2, W);
         hipLaunchKernelGGL((k_mr_pass2<T, 1>), g2, dim3(t2), lds2, s, io, tmp, s2, tw2, (int)n1, (int)n2, W);
     } else {
-        BDSP_TRY(mr_set_lds(k_mr_pass1<T, -1>, lds1));
-        BDSP_TRY(mr_set_lds(k_mr_pass2<T, -1>, lds2));
+        BDSP_TRY(kernel_lds(k_mr_pass1<T, -1>, lds1));
+        BDSP_TRY(kernel_lds(k_mr_pass2<T, -1>, lds2));
         hipLaunchKernelGGL((k_mr_pass1<T, -1>), g1, dim3(t1), lds1, s, io, tmp, s1, tw1, (int)n1, (int)n2, W);
         hipLaunchKernelGGL((k_mr_pass2<T, -1>), g2, dim3(t2), lds2, s, io, tmp, s2, tw2, (int)n1, (int)n2, W);
     }

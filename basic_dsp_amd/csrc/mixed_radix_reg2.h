@@ -1,6 +1,6 @@
 // mixed_radix_reg2.h -- the register-resident TWO-stage mixed-radix kernel for short smooth lengths n = R0 R1 < 300 (100 = 10 10,
-// 120 = 12 10, 240 = 16 15 ...); included by mixed_radix_reg3_f32.hip / _f64.hip next to mixed_radix_reg3.h, whose I/O descriptor
-// (MrReg3Io) and radix set it shares.  Same idea as k_mr_reg3 with one stage less: a thread keeps one radix-R butterfly per stage
+// 120 = 12 10, 240 = 16 15 ...); included by mixed_radix_reg3_f32.hip / _f64.hip next to mixed_radix_reg3.h, whose launch function
+// (mr_reg_launch), I/O descriptor (MrReg3Io, mr_reg_io.h) and radix set it shares.  Same idea as k_mr_reg3 with one stage less: a thread keeps one radix-R butterfly per stage
 // in registers, ONE padded LDS exchange between the two stages, persistent workgroups, the stage-1 twiddles w_n^(r j) per-thread
 // constants loaded once.  A transform is only R0 (the larger radix) threads wide, so a 256-thread workgroup takes 256 / R0 of them
 // at once -- consecutive vectors, i.e. ONE contiguous chunk of the batch: the workgroup brings that chunk into LDS in natural
@@ -9,6 +9,7 @@
 // two rolled loops.  Replaces k_mr_wg for these lengths (table copy per workgroup, four LDS round trips, 1024 threads).
 // f32 only (mixed_radix_reg3_f64.hip says why).  *Measured*: profiles/r06_plan_probe_valid.txt run 5.
 #pragma once
+#include "mr_reg_io.h"
 #include "mixed_radix_reg3.h"
 
 namespace bdsp {
@@ -132,25 +133,8 @@ template <typename T, int R0, int R1>
 static int mr_reg2_run(const MrReg3Io<T>& io, size_t batch, bool inverse, hipStream_t s)
 {
     using P = MrReg2<R0, R1, (int)sizeof(T)>;
-    const cpx<T>* wtab;
-    BDSP_TRY(twiddle_table<T>(P::N, &wtab));
     const size_t lds = sizeof(cpx<T>) * (size_t)P::B * (P::N + P::LA);
-    static int occ = 0;
-    if (occ == 0) {
-        int o = 0;
-        if (lds > 64 * 1024) {
-            BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mr_reg2<T, -1, R0, R1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mr_reg2<T, 1, R0, R1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        }
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k_mr_reg2<T, -1, R0, R1>, P::THREADS, lds) != hipSuccess || o < 1) o = 1;
-        occ = o;
-    }
-    const size_t groups = (batch + P::B - 1) / P::B, slots = (size_t)num_cus() * (size_t)occ;
-    const unsigned grid = (unsigned)(groups < slots ? groups : slots);
-    if (inverse) hipLaunchKernelGGL((k_mr_reg2<T, 1, R0, R1>), dim3(grid), dim3(P::THREADS), lds, s, io, wtab, (unsigned long long)batch);
-    else hipLaunchKernelGGL((k_mr_reg2<T, -1, R0, R1>), dim3(grid), dim3(P::THREADS), lds, s, io, wtab, (unsigned long long)batch);
-    BDSP_LAUNCH_CHECK();
-    return BDSP_OK;
+    return mr_reg_launch(k_mr_reg2<T, -1, R0, R1>, k_mr_reg2<T, 1, R0, R1>, P::N, P::THREADS, P::B, lds, io, batch, inverse, s);
 }
 
 // every n = R0 R1 < 300 that is not a power of two, radices out of k_mr_reg3's set, the smaller radix as large as possible

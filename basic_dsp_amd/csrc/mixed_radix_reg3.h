@@ -4,6 +4,7 @@
 // such a batch never loads).
 #pragma once
 #include "bdsp_internal.h"
+#include "mr_reg_io.h"
 #include "mr_dft.h"
 #include "dsp_funcs.h"
 
@@ -40,26 +41,6 @@ struct MrReg3 {
     static constexpr int SB = R0 * R1 + ((R0 - R0 * R1) % 32 + 32) % 32;
     static constexpr int LB = R2 * SB;
     static_assert(NT <= 512 && B >= 1, "a transform fits a workgroup");
-};
-
-// What the kernel fuses besides the transform: input rotation (ifft_shift), input scale, a window on the input or divided out of
-// the output, real input, output rotation (fft_shift), real-part / magnitude output -- every option k_mr_wg has.  `plain` = none of them: stage 0 loads
-// from HBM and stage 2 stores to it straight from registers.  Otherwise the workgroup stages its transforms' inputs and outputs
-// through the two LDS buffers in natural order, in rolled loops that carry the index arithmetic (with it in the unrolled
-// register code the plain path's f32 kernels went from 84 to 139 VGPRs and the f64 ones lost a wave per SIMD): three more
-// barriers and two more LDS trips per transform for the calls that use an option, nothing for the ones that do not.
-template <typename T>
-struct MrReg3Io {
-    const T* in;
-    T* out;
-    unsigned rot_in, rot_out; // input element i is x[(i + rot_in) mod n]; output element i is X[(i + rot_out) mod n]
-    T in_scale;
-    int in_real;              // the input holds n reals per vector
-    int out_kind;             // 0 complex, 1 real part, 2 magnitude
-    int plain;
-    int window_id;            // >= 0: multiply the input by the window (evaluated like the reference, symmetrically) ...
-    int window_div;           // ... or divide the output by it (windowed_ifft)
-    T alpha;
 };
 
 // OPTS = false: the plain path alone.  Built for the five 512-thread lengths only: with the option code in the same kernel their f32
@@ -176,51 +157,38 @@ __global__ __launch_bounds__((MrReg3<R0, R1, R2>::THREADS)) void k_mr_reg3(MrReg
     }
 }
 
-constexpr int MR_REG3_NOT_BUILT = 1 << 20;
+// One launch of a persistent register-resident kernel (k_mr_reg3, k_mr_reg2), `fwd` or `inv`: as many workgroups as the device
+// holds at once (kernel_slots: the forward kernel's count for both directions), fewer if the batch has fewer groups of `per_wg`.
+template <typename T, typename K>
+static int mr_reg_launch(K* fwd, K* inv, int n, int threads, int per_wg, size_t lds, const MrReg3Io<T>& io, size_t batch,
+                         bool inverse, hipStream_t s)
+{
+    const cpx<T>* wtab;
+    BDSP_TRY(twiddle_table<T>(n, &wtab));
+    int occ = 1;
+    BDSP_TRY(kernel_slots(fwd, threads, lds, &occ));
+    K* const kern = inverse ? inv : fwd;
+    if (inverse) BDSP_TRY(kernel_lds(inv, lds)); // (kernel_slots saw to the forward kernel's limit)
+    const size_t groups = (batch + per_wg - 1) / per_wg, slots = (size_t)num_cus() * (size_t)occ;
+    const unsigned grid = (unsigned)(groups < slots ? groups : slots);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, io, wtab, (unsigned long long)batch);
+    BDSP_LAUNCH_CHECK();
+    return BDSP_OK;
+}
 
 template <typename T, int R0, int R1, int R2>
 static int mr_reg3_run(const MrReg3Io<T>& io, size_t batch, bool inverse, hipStream_t s)
 {
     using P = MrReg3<R0, R1, R2>;
-    const cpx<T>* wtab;
-    BDSP_TRY(twiddle_table<T>(P::N, &wtab));
     const size_t lds = sizeof(cpx<T>) * (size_t)P::B * (P::LA + P::LB);
-    static int occ = 0; // resident workgroups per CU as the runtime computes it (registers and LDS), once per instantiation
-    if (occ == 0) {
-        int o = 0;
-        if (lds > 64 * 1024) {
-            BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mr_reg3<T, -1, R0, R1, R2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mr_reg3<T, 1, R0, R1, R2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        }
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k_mr_reg3<T, -1, R0, R1, R2>, P::THREADS, lds) != hipSuccess || o < 1) o = 1;
-        occ = o;
-    }
-    const size_t groups = (batch + P::B - 1) / P::B, slots = (size_t)num_cus() * (size_t)occ;
-    const unsigned grid = (unsigned)(groups < slots ? groups : slots);
+    auto fwd = k_mr_reg3<T, -1, R0, R1, R2>, inv = k_mr_reg3<T, 1, R0, R1, R2>;
     if constexpr (P::THREADS == 512 && sizeof(T) == 4) {
         if (io.plain) { // the plain-only instantiation: two workgroups per CU (see k_mr_reg3 OPTS)
-            static int occ_plain = 0;
-            if (occ_plain == 0) {
-                int o = 0;
-                if (lds > 64 * 1024) {
-                    BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mr_reg3<T, -1, R0, R1, R2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mr_reg3<T, 1, R0, R1, R2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                }
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, k_mr_reg3<T, -1, R0, R1, R2, false>, P::THREADS, lds) != hipSuccess || o < 1) o = 1;
-                occ_plain = o;
-            }
-            const size_t slots_p = (size_t)num_cus() * (size_t)occ_plain;
-            const unsigned grid_p = (unsigned)(groups < slots_p ? groups : slots_p);
-            if (inverse) hipLaunchKernelGGL((k_mr_reg3<T, 1, R0, R1, R2, false>), dim3(grid_p), dim3(P::THREADS), lds, s, io, wtab, (unsigned long long)batch);
-            else hipLaunchKernelGGL((k_mr_reg3<T, -1, R0, R1, R2, false>), dim3(grid_p), dim3(P::THREADS), lds, s, io, wtab, (unsigned long long)batch);
-            BDSP_LAUNCH_CHECK();
-            return BDSP_OK;
+            fwd = k_mr_reg3<T, -1, R0, R1, R2, false>;
+            inv = k_mr_reg3<T, 1, R0, R1, R2, false>;
         }
     }
-    if (inverse) hipLaunchKernelGGL((k_mr_reg3<T, 1, R0, R1, R2>), dim3(grid), dim3(P::THREADS), lds, s, io, wtab, (unsigned long long)batch);
-    else hipLaunchKernelGGL((k_mr_reg3<T, -1, R0, R1, R2>), dim3(grid), dim3(P::THREADS), lds, s, io, wtab, (unsigned long long)batch);
-    BDSP_LAUNCH_CHECK();
-    return BDSP_OK;
+    return mr_reg_launch(fwd, inv, P::N, P::THREADS, P::B, lds, io, batch, inverse, s);
 }
 
 // The lengths: every n = R0 R1 R2 <= 4096 (f64: <= 2048, like k_mr_wg) that is not a power of two, with radices out of

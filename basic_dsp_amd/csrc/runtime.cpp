@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "bdsp_internal.h"
+#include "launch_cache_core.h"
 
 namespace bdsp {
 
@@ -115,6 +116,33 @@ int num_cus()
     DeviceCtx* c;
     if (ctx_locked(&c) != BDSP_OK) return 256;
     return c->cus > 0 ? c->cus : 256;
+}
+
+// Launch attributes belong to the CURRENT device's copy of a kernel: what both functions remember is keyed by the device
+// ordinal (launch_cache_core.h), so a process that moves to another device raises the limit and asks again there.
+static LaunchCache g_launch;
+
+int kernel_lds(const void* kernel, size_t bytes)
+{
+    int dev = 0;
+    if (bytes <= 64 * 1024) return BDSP_OK; // what every kernel may have
+    BDSP_HIP_TRY(hipGetDevice(&dev));
+    return g_launch.lds_limit(dev, kernel, bytes, [&] {
+        BDSP_HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        return (int)BDSP_OK;
+    });
+}
+
+int kernel_slots(const void* kernel, int threads, size_t lds, int* per_cu)
+{
+    int dev = 0;
+    BDSP_TRY(kernel_lds(kernel, lds));
+    BDSP_HIP_TRY(hipGetDevice(&dev));
+    *per_cu = g_launch.slots(dev, kernel, threads, lds, [&] {
+        int o = 0;
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kernel, threads, lds) == hipSuccess ? o : 0;
+    });
+    return BDSP_OK;
 }
 
 int ws_alloc(void** p, size_t bytes, hipStream_t stream)

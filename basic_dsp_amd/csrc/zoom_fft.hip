@@ -132,9 +132,7 @@ static int zf_launch_wg(const T* x, T* y, const T* pre, const T* post, const T* 
     using F = WgFft<T, L, L / 16>;
     const size_t lds = ((size_t)B * (F::LDS_ELEMS + 1) + 16 * 17) * sizeof(cpx<T>);
     auto k = k_zf_wg<T, L, IN_REAL, ROW_START>;
-    // on every launch: the attribute belongs to the current device's copy of the kernel
-    if (lds > 64 * 1024)
-        BDSP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    BDSP_TRY(kernel_lds(k, lds));
     const size_t groups = (rows + B - 1) / B, slots = (size_t)num_cus() * 4;
     hipLaunchKernelGGL(k, dim3((unsigned)(groups < slots ? groups : slots)), dim3(256), lds, s, x, reinterpret_cast<cpx<T>*>(y),
                        reinterpret_cast<const cpx<T>*>(pre), reinterpret_cast<const cpx<T>*>(post),

@@ -95,11 +95,14 @@ def test_the_unit_has_no_atomic_and_is_in_the_makefile():
     for text in (unit, core):
         assert not re.search(r"^\s+static\s+(?!_assert)", text.replace("static_assert", "static__assert"), re.M)
         assert "thread_local" not in text
-    assert "hipFuncAttributeMaxDynamicSharedMemorySize" in unit
+    # (through kernel_lds of runtime.cpp, the one place that names the attribute)
+    with open(os.path.join(CSRC, "runtime.cpp")) as f:
+        runtime = f.read()
+    assert "hipFuncAttributeMaxDynamicSharedMemorySize" in runtime.split("int kernel_lds(")[1].split("\n}\n")[0]
     launches = list(re.finditer(r"hipLaunchKernelGGL\(kern,", unit))
-    assert len(launches) == 3 and len(re.findall(r"BDSP_TRY\(iir_allow_lds\(kern, lds\)\);", unit)) == 3
+    assert len(launches) == 3 and len(re.findall(r"BDSP_TRY\(kernel_lds\(kern, lds\)\);", unit)) == 3
     for m in launches:  # the line before the launch sets it
-        assert "iir_allow_lds(kern, lds)" in unit[:m.start()].rstrip().splitlines()[-1]
+        assert "kernel_lds(kern, lds)" in unit[:m.start()].rstrip().splitlines()[-1]
     assert "__shfl_up" in unit and "__syncthreads" in unit  # cross-lane inside a wave, LDS across the waves
     # every dispatch constant is named, and its line cites the profile or says that nobody measured it
     for name in ("IIR_TILE", "IIR_MAX_SECTIONS", "IIR_CARRY_BATCH"):

@@ -80,7 +80,11 @@ def test_the_unit_has_no_atomic_and_is_in_the_makefile():
     assert '#include "mat_chol_core.h"' in unit and "__builtin_amdgcn_mfma_f32_32x32x2f32" in unit
     assert '#include "mat_mul_core.h"' in core
     # the attribute for more than 64 KB of dynamic LDS is set before every launch, not once behind a static
-    assert "hipFuncAttributeMaxDynamicSharedMemorySize" in unit and not re.search(r"\bstatic\s+(bool|int)\b[^;(]*;", unit)
+    # (through kernel_lds of runtime.cpp, the one place that names the attribute)
+    with open(os.path.join(CSRC, "runtime.cpp")) as f:
+        runtime = f.read()
+    assert "hipFuncAttributeMaxDynamicSharedMemorySize" in runtime.split("int kernel_lds(")[1].split("\n}\n")[0]
+    assert "BDSP_TRY(kernel_lds(kern, lds));\n    hipLaunchKernelGGL(kern," in unit and not re.search(r"\bstatic\s+(bool|int)\b[^;(]*;", unit)
     # every dispatch threshold is a named constant that cites its line of the profile or says that nobody measured it
     for name in ("LA_SMALL_MAX_N", "LA_SOLVE_MAX_BLOCKS"):
         m = re.search(r"^(.*\n)?.*constexpr size_t %s = \d+;.*$" % name, core, re.M)
