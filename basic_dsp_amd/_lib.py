@@ -362,6 +362,10 @@ for _s, _t, _R in (("32", _F, VectorInteropResult32), ("64", _D, VectorInteropRe
     if hasattr(lib, "bdsp_hip_sosfilt" + _s):  # (as above)
         _proto("bdsp_hip_sosfilt" + _s, C.c_int32, _P, C.POINTER(_D), _SZ, _P)
         _proto(_m + "sosfilt" + _s, C.c_int32, _P, C.POINTER(_D), _SZ, _P)
+    # sliding order statistics along the rows (rank_filter.rank_filter, rank_filter.medfilt): guard -1 is none
+    if hasattr(lib, "bdsp_hip_rank_filter" + _s):  # (as above)
+        _proto("bdsp_hip_rank_filter" + _s, C.c_int32, _P, _SZ, _SZ, C.c_int64, C.c_int32)
+        _proto(_m + "rank_filter" + _s, C.c_int32, _P, _SZ, _SZ, C.c_int64, C.c_int32)
 
 WINDOW_FN32 = C.CFUNCTYPE(_F, _P, _SZ, _SZ)
 WINDOW_FN64 = C.CFUNCTYPE(_D, _P, _SZ, _SZ)

@@ -396,6 +396,12 @@ template <typename T>
 int iir_sosfilt(T* data, size_t rows, size_t n, bool is_complex, const IirSec<T>* tab, size_t S, T* state, const double* m,
                 double* carry, hipStream_t s);
 
+// rank_filter.hip -- the element of rank `rank` of the window guard < |d| <= half (guard < 0: |d| <= half) around every point
+// of rows x n real values, from `in` to `out` (two buffers), in IEEE totalOrder on the bit patterns (rank_filter_core.h);
+// the arguments are valid (rank_args_valid) and half <= RANK_MAX_HALF.  One launch, whatever the row count
+template <typename T>
+int rank_filter_rows(const T* in, T* out, size_t rows, size_t n, size_t half, size_t rank, int64_t guard, int boundary, hipStream_t s);
+
 // zoom_fft.hip -- chirp-z transform of a band: rows x n points -> rows x bins complex, l = zf_conv_len(n, bins)
 // (zoom_fft_core.h); the launch counts do not depend on `rows`
 // the three tables of a plan: pre (n), post (bins) and the wrapped kernel (l, not yet transformed); start reduced modulo

@@ -20,6 +20,7 @@
 #include "mat_chol_core.h"
 #include "mat_eigh_core.h"
 #include "iir_core.h"
+#include "rank_filter_core.h"
 #include "mat_frame_core.h"
 #include "zoom_fft_core.h"
 
@@ -2273,6 +2274,24 @@ int op_sosfilt(DevVec<T>* v, size_t rows, const double* sos, size_t S, DevVec<T>
                           wc.as<double>(), s);
 }
 
+// rank_filter (rank_filter.hip): the element of rank `rank` of the window guard < |d| <= half (guard -1: |d| <= half) around
+// every point of every row of a real vector or matrix (a vector is one row), any domain, in IEEE totalOrder on the bit
+// patterns; the output carries the bits of the selected input.  Nothing of it is in the reference.  An argument error comes
+// first (7, the data untouched), then a poisoned operand (the callers answer -1), then the number kind (4), then what this
+// backend does not implement.  Out of place through the trade buffer, as op_swap: one launch whatever the row count.
+template <typename T>
+int op_rank_filter(DevVec<T>* v, size_t rows, size_t half, size_t rank, int64_t guard, int boundary)
+{
+    if (!rank_args_valid(half, rank, guard, boundary)) return BDSP_ERR_ARG_LENGTH;
+    if (v->erroneous()) return BDSP_OK;
+    if (v->complex_) return BDSP_ERR_MUST_BE_REAL;
+    if (half > (size_t)RANK_MAX_HALF) { set_last_error("rank_filter: half above 1024 (RANK_MAX_HALF)"); return BDSP_ERR_UNSUPPORTED; }
+    if (rows == 0 || v->valid_len == 0) return BDSP_OK;
+    BDSP_TRY(rank_filter_rows<T>(v->data, v->buf, rows, v->valid_len / rows, half, rank, guard, boundary, lib_stream()));
+    v->trade();
+    return BDSP_OK;
+}
+
 // row c, point j = x[j * channels + c]: the transpose of the vector seen as [points / channels][channels]
 template <typename T>
 int mat_from_interleaved(const DevVec<T>* v, size_t channels, DevMat<T>** out)
@@ -3781,6 +3800,17 @@ BDSP_ZOOM_FFT(64, double, MatBuf64, VecBuf64)
 BDSP_SOSFILT(32, float, MatBuf32, VecBuf32)
 BDSP_SOSFILT(64, double, MatBuf64, VecBuf64)
 #undef BDSP_SOSFILT
+
+// sliding order statistics along the rows (op_rank_filter above): a vector is a matrix of one row
+#define BDSP_RANK_FILTER(SFX, T, MB, VB)                                                                    \
+    int32_t bdsp_hip_rank_filter##SFX(VB* vector, size_t half, size_t rank, int64_t guard, int32_t boundary) \
+    { DevVec<T>* v = H<T>(vector); return finish<T>(v, op_rank_filter<T>(v, 1, half, rank, guard, boundary)).result_code; } \
+    int32_t bdsp_hip_mat_rank_filter##SFX(MB* m, size_t half, size_t rank, int64_t guard, int32_t boundary) \
+    { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_rank_filter<T>(&a->v, a->rows, half, rank, guard, boundary)); }
+
+BDSP_RANK_FILTER(32, float, MatBuf32, VecBuf32)
+BDSP_RANK_FILTER(64, double, MatBuf64, VecBuf64)
+#undef BDSP_RANK_FILTER
 
 // ---------------------------------------------------------------------------------------------- B3
 int bdsp_hip_dev_fft(int elem, void* data, void* scratch, size_t points, size_t batch, unsigned flags,

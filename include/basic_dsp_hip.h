@@ -1072,6 +1072,30 @@ int32_t bdsp_hip_mat_eigh32(const MatBuf32 *a, MatBuf32 **w, MatBuf32 **v, int32
  * matrix call is bit-equal to the vector call on that row. */
 int32_t bdsp_hip_sosfilt32(VecBuf32 *v, const double *sos, size_t sections, VecBuf32 *state /* may be NULL */);
 int32_t bdsp_hip_mat_sosfilt32(MatBuf32 *m, const double *sos, size_t sections, MatBuf32 *state /* may be NULL */);
+/* rank_filter: a sliding order statistic along a vector or along every row of a matrix, in place (nothing of it is in
+ * the reference).  The data are real, in any domain; length, domain, delta and number kind stay.  For point i of a row of
+ * n points the window is the multiset x[i + d], guard < |d| <= half; with guard == -1 (none) it is all |d| <= half, the
+ * centre included: W = 2 half + 1 values without a guard, 2 (half - guard) with one.  The result is the window's element
+ * of rank `rank`, 0 the smallest and W - 1 the largest; every result is computed from the row as it was on entry.  The
+ * median filter of an odd kernel size k is half = rank = (k - 1) / 2; rank 0 and W - 1 are the running minimum and
+ * maximum; a guard gives the ordered-statistic CFAR floor of the training cells around every cell.
+ * boundary says how positions outside the row are read: 0 (zero) as +0.0, scipy.signal.medfilt's rule; 1 (wrap) index
+ * mod n, also where half >= n and the window wraps more than once; 2 (nearest) the row's first or last point.
+ * Order: IEEE totalOrder on the bit patterns, -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN: the kernel compares the
+ * keys bits ^ (sign ? all ones : sign bit) as unsigned integers.  The output carries exactly the bits of the selected
+ * input, NaN payloads and denormals included: no flush and no arithmetic touches a value.
+ * Codes: 0; 7, with the data untouched, for rank >= W, guard >= half (or below -1) or an unknown boundary; then -1 for a
+ * poisoned vector or matrix; then 4 (BDSP_ERR_MUST_BE_REAL) for complex data; then BDSP_ERR_UNSUPPORTED for half above
+ * 1024 (RANK_MAX_HALF) and for rows x tiles above 2^31.  No rows, or rows of no points: 0 and nothing changes.
+ * Method: one launch whatever the row count, rows x tiles of 1024 outputs; a workgroup holds its tile and a halo of half
+ * on each side in LDS as integer keys and writes to the trade buffer, which is then swapped in.  Short windows count,
+ * for every candidate, the window keys below it and at or below it (W^2 reads); long windows build the answer key bit
+ * by bit from the top (32 or 64 passes over the window); the choice depends on W and the precision alone.  No atomics,
+ * no early exit, no workgroup waits for another.  Deterministic: the result is a function of the row and the arguments
+ * only, never of the row count, the device's CU count or of timing: row r of the matrix call is bit-equal to the vector
+ * call on that row. */
+int32_t bdsp_hip_rank_filter32(VecBuf32 *v, size_t half, size_t rank, int64_t guard /* -1: none */, int32_t boundary);
+int32_t bdsp_hip_mat_rank_filter32(MatBuf32 *m, size_t half, size_t rank, int64_t guard /* -1: none */, int32_t boundary);
 
 MatBuf64 *bdsp_hip_mat_new64(int32_t is_complex, int32_t domain, size_t rows, size_t row_len, double delta); /* row_len in scalars; zero filled */
 void bdsp_hip_mat_delete64(MatBuf64 *m);
@@ -1255,6 +1279,9 @@ int32_t bdsp_hip_mat_eigh64(const MatBuf64 *a, MatBuf64 **w, MatBuf64 **v, int32
 /* second-order-section filtering: see bdsp_hip_sosfilt32 */
 int32_t bdsp_hip_sosfilt64(VecBuf64 *v, const double *sos, size_t sections, VecBuf64 *state /* may be NULL */);
 int32_t bdsp_hip_mat_sosfilt64(MatBuf64 *m, const double *sos, size_t sections, MatBuf64 *state /* may be NULL */);
+/* sliding order statistics: see bdsp_hip_rank_filter32 */
+int32_t bdsp_hip_rank_filter64(VecBuf64 *v, size_t half, size_t rank, int64_t guard /* -1: none */, int32_t boundary);
+int32_t bdsp_hip_mat_rank_filter64(MatBuf64 *m, size_t half, size_t rank, int64_t guard /* -1: none */, int32_t boundary);
 
 /* ==========================================================================================
  * B3 -- kernels on caller-owned DEVICE memory.  `stream` is a hipStream_t passed as void*
