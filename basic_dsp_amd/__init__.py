@@ -11,6 +11,7 @@ from .spectral import zoom_fft  # noqa: F401
 from .linalg import matmul, cholesky, cholesky_solve, eigh  # noqa: F401
 from .iir import sosfilt  # noqa: F401
 from .rank_filter import rank_filter, medfilt  # noqa: F401
+from .detect import detect, argrelmax  # noqa: F401
 
 __all__ = ["DspVec", "DspMat", "Graph", "BackendError", "lib", "LIB_PATH", "last_error", "require_gpu", "zoom_fft",
-           "matmul", "cholesky", "cholesky_solve", "eigh", "sosfilt", "rank_filter", "medfilt"]
+           "matmul", "cholesky", "cholesky_solve", "eigh", "sosfilt", "rank_filter", "medfilt", "detect", "argrelmax"]

@@ -366,6 +366,11 @@ for _s, _t, _R in (("32", _F, VectorInteropResult32), ("64", _D, VectorInteropRe
     if hasattr(lib, "bdsp_hip_rank_filter" + _s):  # (as above)
         _proto("bdsp_hip_rank_filter" + _s, C.c_int32, _P, _SZ, _SZ, C.c_int64, C.c_int32)
         _proto(_m + "rank_filter" + _s, C.c_int32, _P, _SZ, _SZ, C.c_int64, C.c_int32)
+    # detections of every row as a compact list (detect.detect, detect.argrelmax): handle, kind, threshold, order, boundary,
+    # capacity, counts, index, value
+    if hasattr(lib, "bdsp_hip_detect" + _s):  # (as above)
+        _proto("bdsp_hip_detect" + _s, C.c_int32, _P, C.c_int32, _P, _SZ, C.c_int32, _SZ, _P, _P, _P)
+        _proto(_m + "detect" + _s, C.c_int32, _P, C.c_int32, _P, _SZ, C.c_int32, _SZ, _P, _P, _P)
 
 WINDOW_FN32 = C.CFUNCTYPE(_F, _P, _SZ, _SZ)
 WINDOW_FN64 = C.CFUNCTYPE(_D, _P, _SZ, _SZ)

@@ -402,6 +402,16 @@ int iir_sosfilt(T* data, size_t rows, size_t n, bool is_complex, const IirSec<T>
 template <typename T>
 int rank_filter_rows(const T* in, T* out, size_t rows, size_t n, size_t half, size_t rank, int64_t guard, int boundary, hipStream_t s);
 
+// detect.hip -- the cells of rows x n real values that are above the threshold of `kind` and strict local maxima of `order`
+// (detect_core.h), compacted in row-major order: row_count[row] detections per row, index and value of the first `capacity`
+// (none, and one launch less, where capacity == 0).  rows, n > 0, the arguments are valid (detect_args_valid) and
+// order <= DETECT_MAX_ORDER; all pointers but x's threshold of another kind are device memory.  Four launches, whatever the
+// row count
+template <typename T>
+int detect_rows(const T* x, size_t rows, size_t n, int kind, double t, const double* t_rows, const T* t_cells, size_t t_stride,
+                size_t order, int boundary, size_t capacity, int64_t* tile_ws, int64_t* row_count, int64_t* row_off,
+                int64_t* index, T* value, hipStream_t s);
+
 // zoom_fft.hip -- chirp-z transform of a band: rows x n points -> rows x bins complex, l = zf_conv_len(n, bins)
 // (zoom_fft_core.h); the launch counts do not depend on `rows`
 // the three tables of a plan: pre (n), post (bins) and the wrapped kernel (l, not yet transformed); start reduced modulo

@@ -21,6 +21,7 @@
 #include "mat_eigh_core.h"
 #include "iir_core.h"
 #include "rank_filter_core.h"
+#include "detect_core.h"
 #include "mat_frame_core.h"
 #include "zoom_fft_core.h"
 
@@ -2292,6 +2293,68 @@ int op_rank_filter(DevVec<T>* v, size_t rows, size_t half, size_t rank, int64_t 
     return BDSP_OK;
 }
 
+// detect (detect.hip): the cells of every row of a real vector or matrix (a vector is one row), any domain, that stand above
+// the threshold of `kind` and are strict local maxima of `order`, as counts per row and the first `capacity` (index, value)
+// pairs in row-major order; x is not modified.  Nothing of it is in the reference.  `o` is the operand of kinds 3 (o_rows
+// < 0: a vector) and 4 (a matrix of o_rows rows).  An argument error comes first (7, nothing written), then a poisoned x or
+// operand (-1), then the number kind (4), then the operand's size and meta data as add checks them (7 for the row count,
+// 1, 2), then what this backend does not implement.  Four launches whatever the row count, three where capacity is 0;
+// only the counts and the first min(total, capacity) entries come to the host.
+template <typename T>
+int op_detect(const DevVec<T>* v, size_t rows, bool is_vector, int kind, const void* threshold, const DevVec<T>* o, int64_t o_rows,
+              size_t order, int boundary, size_t capacity, int64_t* counts, int64_t* index, T* value)
+{
+    if (!detect_args_valid(kind, boundary) || !counts || (capacity > 0 && (!index || !value))) return BDSP_ERR_ARG_LENGTH;
+    if ((kind != DETECT_NONE && !threshold) || (is_vector && kind == DETECT_PER_CELL)) return BDSP_ERR_ARG_LENGTH;
+    if (is_vector && kind == DETECT_PER_ROW) kind = DETECT_SCALAR;
+    if (v->erroneous() || (o && o->erroneous())) return BDSP_ERR_POISONED;
+    if (v->complex_ || (o && o->complex_)) return BDSP_ERR_MUST_BE_REAL;
+    const size_t n = rows ? v->valid_len / rows : 0;
+    if (o) {
+        if (kind == DETECT_PER_CELL && (size_t)o_rows != rows) return BDSP_ERR_ARG_LENGTH; // as mat_binary
+        if (o->valid_len != (kind == DETECT_PER_CELL ? v->valid_len : n)) return BDSP_ERR_SAME_SIZE;
+        if (!meta_agrees(v, o)) return BDSP_ERR_META_DATA;
+    }
+    if (order > (size_t)DETECT_MAX_ORDER) { set_last_error("detect: order above 1024 (DETECT_MAX_ORDER)"); return BDSP_ERR_UNSUPPORTED; }
+    const size_t count_rows = is_vector ? 1 : rows;
+    if (rows == 0 || n == 0) {
+        for (size_t r = 0; r < count_rows; ++r) counts[r] = 0;
+        return BDSP_OK;
+    }
+    const size_t tiles = detect_tiles(n);
+    if (rows > 0x7fffffffu / tiles) { set_last_error("detect: rows x tiles above 2^31"); return BDSP_ERR_UNSUPPORTED; }
+    hipStream_t s = lib_stream();
+    const size_t cap = capacity < v->valid_len ? capacity : v->valid_len; // a list is never longer than the data
+    WsBlock wt, wc, wo, wr, wi, wv;
+    BDSP_TRY(wt.alloc(sizeof(int64_t) * rows * tiles, s));
+    BDSP_TRY(wc.alloc(sizeof(int64_t) * rows, s));
+    BDSP_TRY(wo.alloc(sizeof(int64_t) * rows, s));
+    const double* host_t = reinterpret_cast<const double*>(threshold);
+    if (kind == DETECT_PER_ROW) {
+        BDSP_TRY(wr.alloc(sizeof(double) * rows, s));
+        // (pageable memory: the copy has left the caller's array when the call returns)
+        BDSP_HIP_TRY(hipMemcpyAsync(wr.p, host_t, sizeof(double) * rows, hipMemcpyHostToDevice, s));
+    }
+    if (cap) {
+        BDSP_TRY(wi.alloc(sizeof(int64_t) * cap, s));
+        BDSP_TRY(wv.alloc(sizeof(T) * cap, s));
+    }
+    BDSP_TRY(detect_rows<T>(v->data, rows, n, kind, kind == DETECT_SCALAR ? *host_t : 0.0, wr.as<double>(), o ? o->data : nullptr,
+                            kind == DETECT_PER_CELL ? n : 0, order, boundary, cap, wt.as<int64_t>(), wc.as<int64_t>(),
+                            wo.as<int64_t>(), wi.as<int64_t>(), wv.as<T>(), s));
+    BDSP_HIP_TRY(hipMemcpyAsync(counts, wc.p, sizeof(int64_t) * rows, hipMemcpyDeviceToHost, s));
+    BDSP_HIP_TRY(hipStreamSynchronize(s));
+    uint64_t total = 0;
+    for (size_t r = 0; r < rows; ++r) total += (uint64_t)counts[r];
+    const size_t listed = total < cap ? (size_t)total : cap;
+    if (listed) {
+        BDSP_HIP_TRY(hipMemcpyAsync(index, wi.p, sizeof(int64_t) * listed, hipMemcpyDeviceToHost, s));
+        BDSP_HIP_TRY(hipMemcpyAsync(value, wv.p, sizeof(T) * listed, hipMemcpyDeviceToHost, s));
+        BDSP_HIP_TRY(hipStreamSynchronize(s));
+    }
+    return BDSP_OK;
+}
+
 // row c, point j = x[j * channels + c]: the transpose of the vector seen as [points / channels][channels]
 template <typename T>
 int mat_from_interleaved(const DevVec<T>* v, size_t channels, DevMat<T>** out)
@@ -3811,6 +3874,24 @@ BDSP_SOSFILT(64, double, MatBuf64, VecBuf64)
 BDSP_RANK_FILTER(32, float, MatBuf32, VecBuf32)
 BDSP_RANK_FILTER(64, double, MatBuf64, VecBuf64)
 #undef BDSP_RANK_FILTER
+
+// detections of every row as a compact list (op_detect above): a vector is a matrix of one row
+#define BDSP_DETECT(SFX, T, MB, VB)                                                                         \
+    int32_t bdsp_hip_detect##SFX(const VB* vector, int32_t kind, const void* threshold, size_t order, int32_t boundary, \
+                                 size_t capacity, int64_t* counts, int64_t* index, T* value)                \
+    { const DevVec<T>* o = kind == DETECT_PROFILE && threshold ? H<T>(reinterpret_cast<const VB*>(threshold)) : nullptr; \
+      return op_detect<T>(H<T>(vector), 1, true, kind, threshold, o, -1, order, boundary, capacity, counts, index, value); } \
+    int32_t bdsp_hip_mat_detect##SFX(const MB* m, int32_t kind, const void* threshold, size_t order, int32_t boundary, \
+                                     size_t capacity, int64_t* counts, int64_t* index, T* value)            \
+    { const DevMat<T>* a = MC##SFX(m);                                                                      \
+      const DevMat<T>* om = kind == DETECT_PER_CELL && threshold ? MC##SFX(reinterpret_cast<const MB*>(threshold)) : nullptr; \
+      const DevVec<T>* o = om ? &om->v : kind == DETECT_PROFILE && threshold ? H<T>(reinterpret_cast<const VB*>(threshold)) : nullptr; \
+      return op_detect<T>(&a->v, a->rows, false, kind, threshold, o, om ? (int64_t)om->rows : -1, order, boundary, capacity, \
+                          counts, index, value); }
+
+BDSP_DETECT(32, float, MatBuf32, VecBuf32)
+BDSP_DETECT(64, double, MatBuf64, VecBuf64)
+#undef BDSP_DETECT
 
 // ---------------------------------------------------------------------------------------------- B3
 int bdsp_hip_dev_fft(int elem, void* data, void* scratch, size_t points, size_t batch, unsigned flags,

@@ -1096,6 +1096,38 @@ int32_t bdsp_hip_mat_sosfilt32(MatBuf32 *m, const double *sos, size_t sections, 
  * call on that row. */
 int32_t bdsp_hip_rank_filter32(VecBuf32 *v, size_t half, size_t rank, int64_t guard /* -1: none */, int32_t boundary);
 int32_t bdsp_hip_mat_rank_filter32(MatBuf32 *m, size_t half, size_t rank, int64_t guard /* -1: none */, int32_t boundary);
+/* detect: the detections of a vector, or of every row of a matrix, as a compact list (nothing of it is in the reference).
+ * The data are real, in any domain, and are not modified.  Cell j of a row of n points is a detection iff it is above the
+ * threshold and a strict local maximum of order `order`.
+ * Threshold, by kind: 0 none (threshold NULL); 1 one value, double(x[j]) > t (const double * to one value); 2 one value
+ * per row, double(x[r][j]) > t[r] (const double * to rows values; on a vector it means one value); 3 one profile for all
+ * rows, x[r][j] > t[j] (const VecBuf * of n points of the same precision); 4 one value per cell, x[r][j] > t[r][j] (const
+ * MatBuf * of rows x n).  Every comparison is IEEE >: a NaN on either side is never a detection, -0 is not above +0,
+ * denormals compare by value, +inf > t holds for finite t.
+ * Strict local maximum: for every d with 0 < |d| <= order, x[j] > x[j + d]; order 0 is no condition.  boundary says how
+ * positions outside the row are read: 0 (open) the comparison is skipped, so an end point can be a peak and with n = 1
+ * every cell passes; 1 (wrap) index mod n, any number of turns, so order >= n compares a cell with itself and detects
+ * nothing; 2 (nearest) the end point repeated, scipy.signal.argrelmax's mode "clip": an end point is never a peak for
+ * order >= 1.  Plateaus yield no peak; a NaN neighbour blocks a peak.
+ * Outputs: counts[r] is always the true number of detections of row r (one entry for a vector); index and value receive
+ * the first min(total, capacity) detections in row-major order, rows ascending and index ascending within a row; value
+ * holds exactly the bits of the detected input.  The row of an entry follows from counts.  With capacity 0 the two lists
+ * may be NULL and the write launch is skipped.
+ * Codes: 0; 7, with nothing written, for an unknown kind or boundary, a NULL counts, a NULL threshold of a kind that has
+ * one, NULL lists with capacity > 0, or kind 4 on a vector; then -1 for a poisoned x or operand; then 4
+ * (BDSP_ERR_MUST_BE_REAL) for a complex x or operand; then, for kinds 3 and 4, the size and meta-data checks of add with
+ * its codes (7 for another row count, 1, 2); then BDSP_ERR_UNSUPPORTED for order above 1024 (DETECT_MAX_ORDER) and for
+ * rows x tiles above 2^31.  No rows, or rows of no points: 0 with counts zeroed.
+ * Method: four launches whatever the row count: the count of every tile of 1024 cells (a workgroup holds its tile and a
+ * halo of order on each side in LDS; a wave's 64-bit ballot counts 64 consecutive cells), the prefix over the tiles of
+ * each row, the prefix over the rows (both 64-bit), and the tile launch again, which stores every detection at its slot.
+ * x is read twice; only counts and the listed entries are copied to the host.  No atomics, no workgroup waits for
+ * another.  Deterministic: the list is a function of the data and the arguments only, never of the row count, the
+ * device's CU count or of timing: row r of the matrix call equals the vector call on that row. */
+int32_t bdsp_hip_detect32(const VecBuf32 *v, int32_t kind, const void *threshold, size_t order, int32_t boundary,
+                          size_t capacity, int64_t *counts /* 1 */, int64_t *index /* capacity */, float *value /* capacity */);
+int32_t bdsp_hip_mat_detect32(const MatBuf32 *m, int32_t kind, const void *threshold, size_t order, int32_t boundary,
+                              size_t capacity, int64_t *counts /* rows */, int64_t *index, float *value);
 
 MatBuf64 *bdsp_hip_mat_new64(int32_t is_complex, int32_t domain, size_t rows, size_t row_len, double delta); /* row_len in scalars; zero filled */
 void bdsp_hip_mat_delete64(MatBuf64 *m);
@@ -1282,6 +1314,11 @@ int32_t bdsp_hip_mat_sosfilt64(MatBuf64 *m, const double *sos, size_t sections, 
 /* sliding order statistics: see bdsp_hip_rank_filter32 */
 int32_t bdsp_hip_rank_filter64(VecBuf64 *v, size_t half, size_t rank, int64_t guard /* -1: none */, int32_t boundary);
 int32_t bdsp_hip_mat_rank_filter64(MatBuf64 *m, size_t half, size_t rank, int64_t guard /* -1: none */, int32_t boundary);
+/* detections as a compact list: see bdsp_hip_detect32 */
+int32_t bdsp_hip_detect64(const VecBuf64 *v, int32_t kind, const void *threshold, size_t order, int32_t boundary,
+                          size_t capacity, int64_t *counts /* 1 */, int64_t *index /* capacity */, double *value /* capacity */);
+int32_t bdsp_hip_mat_detect64(const MatBuf64 *m, int32_t kind, const void *threshold, size_t order, int32_t boundary,
+                              size_t capacity, int64_t *counts /* rows */, int64_t *index, double *value);
 
 /* ==========================================================================================
  * B3 -- kernels on caller-owned DEVICE memory.  `stream` is a hipStream_t passed as void*
