@@ -12,6 +12,8 @@ from .linalg import matmul, cholesky, cholesky_solve, eigh  # noqa: F401
 from .iir import sosfilt  # noqa: F401
 from .rank_filter import rank_filter, medfilt  # noqa: F401
 from .detect import detect, argrelmax  # noqa: F401
+from .sorting import sort, argsort, top_k, quantile, median  # noqa: F401
 
 __all__ = ["DspVec", "DspMat", "Graph", "BackendError", "lib", "LIB_PATH", "last_error", "require_gpu", "zoom_fft",
-           "matmul", "cholesky", "cholesky_solve", "eigh", "sosfilt", "rank_filter", "medfilt", "detect", "argrelmax"]
+           "matmul", "cholesky", "cholesky_solve", "eigh", "sosfilt", "rank_filter", "medfilt", "detect", "argrelmax",
+           "sort", "argsort", "top_k", "quantile", "median"]

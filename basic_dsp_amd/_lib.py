@@ -371,6 +371,13 @@ for _s, _t, _R in (("32", _F, VectorInteropResult32), ("64", _D, VectorInteropRe
     if hasattr(lib, "bdsp_hip_detect" + _s):  # (as above)
         _proto("bdsp_hip_detect" + _s, C.c_int32, _P, C.c_int32, _P, _SZ, C.c_int32, _SZ, _P, _P, _P)
         _proto(_m + "detect" + _s, C.c_int32, _P, C.c_int32, _P, _SZ, C.c_int32, _SZ, _P, _P, _P)
+    # order statistics of every row (sorting.sort, argsort, top_k, quantile, median): handle, descending; and handle,
+    # descending, count, ranks, index, value
+    if hasattr(lib, "bdsp_hip_sort" + _s):  # (as above)
+        _proto("bdsp_hip_sort" + _s, C.c_int32, _P, C.c_int32)
+        _proto(_m + "sort" + _s, C.c_int32, _P, C.c_int32)
+        _proto("bdsp_hip_order_select" + _s, C.c_int32, _P, C.c_int32, _SZ, _P, _P, _P)
+        _proto(_m + "order_select" + _s, C.c_int32, _P, C.c_int32, _SZ, _P, _P, _P)
 
 WINDOW_FN32 = C.CFUNCTYPE(_F, _P, _SZ, _SZ)
 WINDOW_FN64 = C.CFUNCTYPE(_D, _P, _SZ, _SZ)

@@ -412,6 +412,18 @@ int detect_rows(const T* x, size_t rows, size_t n, int kind, double t, const dou
                 size_t order, int boundary, size_t capacity, int64_t* tile_ws, int64_t* row_count, int64_t* row_off,
                 int64_t* index, T* value, hipStream_t s);
 
+// sort.hip -- every row of rows x n real values in IEEE totalOrder on the bit patterns (descending: the ascending order of the
+// complemented keys), sort_core.h; rows, n > 0 and sort_supported(rows, n).  sort_rows: between data and buf, the result in buf
+// iff *in_buf; 1 + P launches, P = ceil(log2(ceil(n / SORT_TILE))).  sort_select_rows: x is not modified; (key, u32 index)
+// pairs travel in ws_a and ws_b (sort_select_ws_bytes each; ws_b only where a row is more than one tile), index and value
+// (device, rows x count entries, each may be null) receive the elements of the sorted ranks `ranks` (device, count values
+// below n; null: 0 .. count - 1); 2 + P launches, whatever the row count
+template <typename T> int sort_rows(T* data, T* buf, size_t rows, size_t n, bool descending, bool* in_buf, hipStream_t s);
+size_t sort_select_ws_bytes(size_t rows, size_t n, size_t key_bytes);
+template <typename T>
+int sort_select_rows(const T* x, size_t rows, size_t n, bool descending, size_t count, const uint64_t* ranks, void* ws_a, void* ws_b,
+                     int64_t* index, T* value, hipStream_t s);
+
 // zoom_fft.hip -- chirp-z transform of a band: rows x n points -> rows x bins complex, l = zf_conv_len(n, bins)
 // (zoom_fft_core.h); the launch counts do not depend on `rows`
 // the three tables of a plan: pre (n), post (bins) and the wrapped kernel (l, not yet transformed); start reduced modulo

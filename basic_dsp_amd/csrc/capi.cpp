@@ -22,6 +22,7 @@
 #include "iir_core.h"
 #include "rank_filter_core.h"
 #include "detect_core.h"
+#include "sort_core.h"
 #include "mat_frame_core.h"
 #include "zoom_fft_core.h"
 
@@ -2355,6 +2356,62 @@ int op_detect(const DevVec<T>* v, size_t rows, bool is_vector, int kind, const v
     return BDSP_OK;
 }
 
+// sort (sort.hip): every row of a real vector or matrix (a vector is one row), any domain, in IEEE totalOrder on the bit
+// patterns, ascending or (descending != 0) in the stable ascending order of the complemented keys; the output carries the bits
+// of the inputs.  Nothing of it is in the reference.  An argument error comes first (7, the data untouched), then a poisoned
+// operand (the callers answer -1), then the number kind (4), then what this backend does not implement.  1 + P launches, P =
+// ceil(log2(ceil(n / SORT_TILE))), between the live and the trade buffer: a trade iff the last launch wrote the trade buffer.
+template <typename T>
+int op_sort(DevVec<T>* v, size_t rows, int descending)
+{
+    if (descending != 0 && descending != 1) return BDSP_ERR_ARG_LENGTH;
+    if (v->erroneous()) return BDSP_OK;
+    if (v->complex_) return BDSP_ERR_MUST_BE_REAL;
+    if (rows == 0 || v->valid_len == 0) return BDSP_OK;
+    const size_t n = v->valid_len / rows;
+    if (!sort_supported(rows, n)) { set_last_error("sort: n at or above 2^32, or rows x tiles above 2^31"); return BDSP_ERR_UNSUPPORTED; }
+    bool in_buf = false;
+    BDSP_TRY(sort_rows<T>(v->data, v->buf, rows, n, descending != 0, &in_buf, lib_stream()));
+    if (in_buf) v->trade();
+    return BDSP_OK;
+}
+
+// order_select (sort.hip): the elements of the sorted ranks ranks[0 .. count) (NULL: 0 .. count - 1) of every row of a real
+// vector or matrix, as rows x count (index, value) entries on the host; x is not modified.  argsort, top_k, quantile and median
+// are this call.  An argument error comes first (7, nothing written: a flag that is not 0 or 1, a rank at or above n, count
+// above n without ranks), then a poisoned x (-1), then the number kind (4), then what this backend does not implement.
+// 2 + P launches whatever the row count, one synchronisation; only the rows x count entries come to the host.
+template <typename T>
+int op_order_select(const DevVec<T>* v, size_t rows, int descending, size_t count, const uint64_t* ranks, int64_t* index, T* value)
+{
+    const size_t n = rows ? v->valid_len / rows : 0;
+    if (descending != 0 && descending != 1) return BDSP_ERR_ARG_LENGTH;
+    if (!ranks && count > n) return BDSP_ERR_ARG_LENGTH;
+    for (size_t j = 0; ranks && j < count; ++j)
+        if (ranks[j] >= n) return BDSP_ERR_ARG_LENGTH;
+    if (v->erroneous()) return BDSP_ERR_POISONED;
+    if (v->complex_) return BDSP_ERR_MUST_BE_REAL;
+    if (rows == 0 || n == 0 || count == 0 || (!index && !value)) return BDSP_OK;
+    if (!sort_supported(rows, n)) { set_last_error("order_select: n at or above 2^32, or rows x tiles above 2^31"); return BDSP_ERR_UNSUPPORTED; }
+    hipStream_t s = lib_stream();
+    const size_t entries = rows * count, ws = sort_select_ws_bytes(rows, n, sizeof(T));
+    WsBlock wa, wb, wr, wi, wv;
+    BDSP_TRY(wa.alloc(ws, s));
+    if (sort_plan(rows, n).passes > 0) BDSP_TRY(wb.alloc(ws, s));
+    if (ranks) {
+        BDSP_TRY(wr.alloc(sizeof(uint64_t) * count, s));
+        // (pageable memory: the copy has left the caller's array when the call returns)
+        BDSP_HIP_TRY(hipMemcpyAsync(wr.p, ranks, sizeof(uint64_t) * count, hipMemcpyHostToDevice, s));
+    }
+    if (index) BDSP_TRY(wi.alloc(sizeof(int64_t) * entries, s));
+    if (value) BDSP_TRY(wv.alloc(sizeof(T) * entries, s));
+    BDSP_TRY(sort_select_rows<T>(v->data, rows, n, descending != 0, count, wr.as<uint64_t>(), wa.p, wb.p, wi.as<int64_t>(), wv.as<T>(), s));
+    if (index) BDSP_HIP_TRY(hipMemcpyAsync(index, wi.p, sizeof(int64_t) * entries, hipMemcpyDeviceToHost, s));
+    if (value) BDSP_HIP_TRY(hipMemcpyAsync(value, wv.p, sizeof(T) * entries, hipMemcpyDeviceToHost, s));
+    BDSP_HIP_TRY(hipStreamSynchronize(s));
+    return BDSP_OK;
+}
+
 // row c, point j = x[j * channels + c]: the transpose of the vector seen as [points / channels][channels]
 template <typename T>
 int mat_from_interleaved(const DevVec<T>* v, size_t channels, DevMat<T>** out)
@@ -3892,6 +3949,21 @@ BDSP_RANK_FILTER(64, double, MatBuf64, VecBuf64)
 BDSP_DETECT(32, float, MatBuf32, VecBuf32)
 BDSP_DETECT(64, double, MatBuf64, VecBuf64)
 #undef BDSP_DETECT
+
+// order statistics of every row (op_sort and op_order_select above): a vector is a matrix of one row
+#define BDSP_SORT(SFX, T, MB, VB)                                                                           \
+    int32_t bdsp_hip_sort##SFX(VB* vector, int32_t descending)                                              \
+    { DevVec<T>* v = H<T>(vector); return finish<T>(v, op_sort<T>(v, 1, descending)).result_code; }         \
+    int32_t bdsp_hip_mat_sort##SFX(MB* m, int32_t descending)                                               \
+    { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_sort<T>(&a->v, a->rows, descending)); }            \
+    int32_t bdsp_hip_order_select##SFX(const VB* vector, int32_t descending, size_t count, const uint64_t* ranks, int64_t* index, void* value) \
+    { return op_order_select<T>(H<T>(vector), 1, descending, count, ranks, index, reinterpret_cast<T*>(value)); } \
+    int32_t bdsp_hip_mat_order_select##SFX(const MB* m, int32_t descending, size_t count, const uint64_t* ranks, int64_t* index, void* value) \
+    { const DevMat<T>* a = MC##SFX(m); return op_order_select<T>(&a->v, a->rows, descending, count, ranks, index, reinterpret_cast<T*>(value)); }
+
+BDSP_SORT(32, float, MatBuf32, VecBuf32)
+BDSP_SORT(64, double, MatBuf64, VecBuf64)
+#undef BDSP_SORT
 
 // ---------------------------------------------------------------------------------------------- B3
 int bdsp_hip_dev_fft(int elem, void* data, void* scratch, size_t points, size_t batch, unsigned flags,

@@ -1128,6 +1128,37 @@ int32_t bdsp_hip_detect32(const VecBuf32 *v, int32_t kind, const void *threshold
                           size_t capacity, int64_t *counts /* 1 */, int64_t *index /* capacity */, float *value /* capacity */);
 int32_t bdsp_hip_mat_detect32(const MatBuf32 *m, int32_t kind, const void *threshold, size_t order, int32_t boundary,
                               size_t capacity, int64_t *counts /* rows */, int64_t *index, float *value);
+/* sort, order_select: the order statistics of a vector, or of every row of a matrix (nothing of it is in the reference).
+ * The data are real, in any domain; n is the points of a row.
+ * Order: ascending is IEEE totalOrder on the bit patterns, -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN, realised as the
+ * unsigned keys k = bits ^ (sign ? all ones : sign bit); ties are broken by ascending index.  Descending is the stable
+ * ascending sort of the complemented key ~k: largest first, and among equal bit patterns the lower index first; it is not
+ * the reverse of the ascending permutation.  Every output carries exactly the bits of the selected input, NaN payloads and
+ * denormals included: no flush and no arithmetic touches a value.
+ * sort sorts every row in place; length, domain, delta and number kind stay.  order_select leaves x as it is and writes, for
+ * every row, the elements of the sorted ranks ranks[0 .. count): index (the position in the row) and value (its bits, float
+ * or double), rows x count row-major entries each, to host arrays.  argsort is count = n, top_k is count = k, a quantile
+ * selects its one or two ranks; a top_k is the full sort and a crop.
+ * Codes: 0; 7, with the data untouched and nothing written, for a descending that is not 0 or 1, a rank at or above n, or
+ * count above n without ranks; then -1 for a poisoned x; then 4 (BDSP_ERR_MUST_BE_REAL) for complex data; then
+ * BDSP_ERR_UNSUPPORTED for n at or above 2^32 and for rows x tiles above 2^31.  No rows, or rows of no points: 0, nothing
+ * changes and nothing is written; count 0 likewise.
+ * Method: a tile launch, in which a workgroup of 256 lanes sorts 4096 elements (SORT_TILE: one tile of a long row, or
+ * 4096 / p rows of at most p points, p a power of two <= 2048) with a bitonic network, 16 elements per lane in registers and
+ * the longer compare distances through LDS; then P = ceil(log2(ceil(n / 4096))) merge launches, each merging neighbouring
+ * runs by the merge path (ties to the left run) and a bitonic merge of 4096 outputs per workgroup.  sort: 1 + P launches
+ * between the live and the trade buffer, keys travel as keys and the last launch turns them back into bits.  order_select:
+ * 2 + P launches (the last gathers the ranks), (key, 32-bit index) pairs in two workspaces of rows x n x (4 + 4) or (8 + 4)
+ * bytes (one where n <= 4096), one synchronisation, and only the rows x count entries are copied to the host.  No atomics,
+ * no workgroup waits for another, no loop leaves early: launch count and work depend on (rows, n, precision, with or
+ * without index) only.  Deterministic: the result is a function of the input bits alone, never of the row count, the
+ * device's CU count or of timing: row r of the matrix call equals the vector call on that row. */
+int32_t bdsp_hip_sort32(VecBuf32 *v, int32_t descending);
+int32_t bdsp_hip_mat_sort32(MatBuf32 *m, int32_t descending);
+/* the elements of sorted ranks ranks[0..count) of every row, as rows x count row-major entries; ranks: a host array, each
+ * < n, any order, repeats allowed; NULL: 0 .. count - 1 (count <= n).  index and value may each be NULL.  x is not modified. */
+int32_t bdsp_hip_order_select32(const VecBuf32 *v, int32_t descending, size_t count, const uint64_t *ranks, int64_t *index, void *value);
+int32_t bdsp_hip_mat_order_select32(const MatBuf32 *m, int32_t descending, size_t count, const uint64_t *ranks, int64_t *index, void *value);
 
 MatBuf64 *bdsp_hip_mat_new64(int32_t is_complex, int32_t domain, size_t rows, size_t row_len, double delta); /* row_len in scalars; zero filled */
 void bdsp_hip_mat_delete64(MatBuf64 *m);
@@ -1319,6 +1350,11 @@ int32_t bdsp_hip_detect64(const VecBuf64 *v, int32_t kind, const void *threshold
                           size_t capacity, int64_t *counts /* 1 */, int64_t *index /* capacity */, double *value /* capacity */);
 int32_t bdsp_hip_mat_detect64(const MatBuf64 *m, int32_t kind, const void *threshold, size_t order, int32_t boundary,
                               size_t capacity, int64_t *counts /* rows */, int64_t *index, double *value);
+/* order statistics of every row: see bdsp_hip_sort32 */
+int32_t bdsp_hip_sort64(VecBuf64 *v, int32_t descending);
+int32_t bdsp_hip_mat_sort64(MatBuf64 *m, int32_t descending);
+int32_t bdsp_hip_order_select64(const VecBuf64 *v, int32_t descending, size_t count, const uint64_t *ranks, int64_t *index, void *value);
+int32_t bdsp_hip_mat_order_select64(const MatBuf64 *m, int32_t descending, size_t count, const uint64_t *ranks, int64_t *index, void *value);
 
 /* ==========================================================================================
  * B3 -- kernels on caller-owned DEVICE memory.  `stream` is a hipStream_t passed as void*
