@@ -159,7 +159,6 @@ template <typename T> int ew_complex_to_real(const T* x, T* out, size_t len, int
 template <typename T> int ew_window(T* x, size_t len, bool is_complex, int id, T alpha, bool unapply, hipStream_t s);
 template <typename T> int ew_window_rows(T* x, size_t rows, size_t row_len, bool is_complex, int id, T alpha, bool unapply, hipStream_t s);
 template <typename T> int ew_fill(T* x, size_t len, T value, hipStream_t s);
-template <typename T> int ew_freq_response(T* x, size_t len, bool is_complex, int fid, T rolloff, T ratio, bool shifted, hipStream_t s);
 template <typename T> int ew_freq_response_rows(T* x, size_t rows, size_t row_len, bool is_complex, int fid, T rolloff, T ratio, bool shifted, hipStream_t s);
 template <typename T> int ew_linear_phase(T* x, size_t len, T delay, hipStream_t s);
 // spectrum of N points -> dst_points, out of place, one trip (mode 0: periodic repetition = the transform of the
@@ -170,7 +169,6 @@ template <typename T> int ew_spectrum_resample(const T* in, T* out, size_t src_p
 // reorg.hip
 template <typename T> int rg_wrap_copy(const T* in, T* out, size_t points, size_t elem, size_t total, long long start, hipStream_t s);
 template <typename T> int rg_zero_interleave(const T* in, T* out, size_t len, size_t elem, size_t factor, hipStream_t s);
-template <typename T> int rg_decimate(const T* in, T* out, size_t out_points, size_t elem, size_t factor, size_t delay, hipStream_t s);
 
 // interp.hip
 template <typename T>
@@ -274,7 +272,8 @@ template <typename T> int ms_unwrap(T* x, size_t rows, size_t row_len, T divisor
 template <typename T>
 int rs_spectrum_rows(const T* in, T* out, size_t rows, size_t src_points, size_t dst_points, int mode, int fid, T rolloff,
                      T ratio, double phase_inc, hipStream_t s);
-// rg_decimate for `rows` rows of `points` elements (elem scalars each) -> out_points elements; one launch
+// out[row][j] = in[row][delay + j * factor] for `rows` rows of `points` elements (elem scalars each) -> out_points
+// elements (a vector is one row); one launch
 template <typename T>
 int rs_decimate_rows(const T* in, T* out, size_t rows, size_t points, size_t out_points, size_t elem, size_t factor,
                      size_t delay, hipStream_t s);

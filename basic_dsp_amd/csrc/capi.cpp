@@ -935,16 +935,19 @@ int op_fft(DevVec<T>* v, bool inverse, bool shift, int window /* -1 none */, siz
     return BDSP_OK;
 }
 
+// `rows` equally long rows back to back, every row with the ONE impulse response h (a vector is one row; the matrix
+// entry passes its rows, matrix/src/time_freq.rs:421-431): the batched launches of op_fft
 template <typename T>
-int op_convolve_signal(DevVec<T>* v, const DevVec<T>* h)
+int op_convolve_signal(DevVec<T>* v, const DevVec<T>* h, size_t rows = 1)
 {
     if (!meta_agrees(v, h)) return BDSP_ERR_META_DATA;  // convolution.rs:485
     if (v->freq) return BDSP_ERR_MUST_BE_TIME;           // :486-488
-    if (v->points() < h->points()) return BDSP_ERR_ARG_LENGTH; // :490-492
-    if (v->points() == 0 || h->points() == 0) return BDSP_OK;
+    const size_t p = rows ? v->points() / rows : 0;
+    if (p < h->points()) return BDSP_ERR_ARG_LENGTH; // :490-492
+    if (p == 0 || h->points() == 0) return BDSP_OK;
     hipStream_t s = lib_stream();
-    if (v->complex_) BDSP_TRY(conv_complex_dev<T>(v->data, v->buf, v->points(), 1, h->data, h->points(), s));
-    else BDSP_TRY(conv_real_dev<T>(v->data, v->buf, v->points(), h->data, h->points(), s));
+    if (v->complex_) BDSP_TRY(conv_complex_dev<T>(v->data, v->buf, p, rows, h->data, h->points(), s));
+    else BDSP_TRY(conv_real_dev<T>(v->data, v->buf, p, h->data, h->points(), s, rows));
     v->trade();
     return BDSP_OK;
 }
@@ -1162,25 +1165,27 @@ int op_interpolate(DevVec<T>* v, int fid, T rolloff, size_t dest_points, T delay
     return BDSP_OK;
 }
 
+// `rows` equally long rows back to back (a vector is one row; the matrix entry passes its rows): one launch
 template <typename T>
-int op_decimatei(DevVec<T>* v, unsigned factor, unsigned delay)
+int op_decimatei(DevVec<T>* v, unsigned factor, unsigned delay, size_t rows = 1)
 {
     if (factor == 0) return BDSP_ERR_ARG_LENGTH;
-    const size_t elem = v->complex_ ? 2 : 1, points = v->points();
+    if (rows == 0) return BDSP_OK;
+    const size_t elem = v->complex_ ? 2 : 1, points = v->points() / rows;
     const size_t outp = delay < points ? (points - delay + factor - 1) / factor : 0;
     if (outp) {
-        BDSP_TRY(rg_decimate<T>(v->data, v->buf, outp, elem, factor, delay, lib_stream()));
+        BDSP_TRY(rs_decimate_rows<T>(v->data, v->buf, rows, points, outp, elem, factor, delay, lib_stream()));
         v->trade();
     }
-    v->valid_len = outp * elem;
+    v->valid_len = rows * outp * elem;
     return BDSP_OK;
 }
 
 template <typename T>
-int op_multiply_frequency_response(DevVec<T>* v, int fid, T rolloff, T ratio)
+int op_multiply_frequency_response(DevVec<T>* v, int fid, T rolloff, T ratio, size_t rows = 1)
 {
     if (!v->freq) { v->poison(); return BDSP_OK; } // convolution.rs:590-593
-    return ew_freq_response<T>(v->data, v->valid_len, v->complex_, fid, rolloff, ratio, false, lib_stream());
+    return ew_freq_response_rows<T>(v->data, rows, rows ? v->valid_len / rows : 0, v->complex_, fid, rolloff, ratio, false, lib_stream());
 }
 
 // Symmetric real FFT family (time_to_freq.rs:188-298, freq_to_time.rs:180-248): a real vector of odd
@@ -1346,13 +1351,14 @@ int op_get_complex_to_real(DevVec<T>* v, DevVec<T>* dst, int kind)
     return rc == BDSP_OK ? 9 : rc;
 }
 
+// every one of `rows` rows (.)= the same shorter vector (a vector is one row; mat_*_smaller_vector pass theirs)
 template <typename T>
-int op_binary_smaller(DevVec<T>* v, const DevVec<T>* o, int op)
+int op_binary_smaller(DevVec<T>* v, const DevVec<T>* o, int op, size_t rows = 1)
 {
-    if (o->valid_len == 0 || v->valid_len % o->valid_len != 0) return BDSP_ERR_ARG_LENGTH; // elementary.rs:613-617
+    const size_t rl = rows ? v->valid_len / rows : 0, e = v->complex_ ? 2 : 1;
+    if (o->valid_len == 0 || rl % o->valid_len != 0) return BDSP_ERR_ARG_LENGTH; // elementary.rs:613-617
     if (!meta_agrees(v, o)) return BDSP_ERR_META_DATA;
-    const size_t e = v->complex_ ? 2 : 1;
-    return mw_smaller<T>(v->data, o->data, 1, v->valid_len / e, o->valid_len / e, 0, v->complex_, op, lib_stream());
+    return mw_smaller<T>(v->data, o->data, rows, rl / e, o->valid_len / e, 0, v->complex_, op, lib_stream());
 }
 
 // Host-sampled callbacks (interop/src/lib.rs:245-377).  A window callback is sampled for every point
@@ -2461,22 +2467,6 @@ int mat_zero_interleave(DevMat<T>* m, int factor)
     return BDSP_OK;
 }
 
-// convolve_signal with ONE impulse response shared by all rows (matrix/src/time_freq.rs:421-431)
-template <typename T>
-int mat_convolve_signal(DevMat<T>* m, const DevVec<T>* h)
-{
-    if (!meta_agrees(&m->v, h)) return BDSP_ERR_META_DATA;
-    if (m->v.freq) return BDSP_ERR_MUST_BE_TIME;
-    const size_t p = m->row_points();
-    if (p < h->points()) return BDSP_ERR_ARG_LENGTH;
-    if (p == 0 || h->points() == 0 || m->rows == 0) return BDSP_OK;
-    hipStream_t s = lib_stream();
-    if (m->v.complex_) BDSP_TRY(conv_complex_dev<T>(m->v.data, m->v.buf, p, m->rows, h->data, h->points(), s));
-    else BDSP_TRY(conv_real_dev<T>(m->v.data, m->v.buf, p, h->data, h->points(), s, m->rows));
-    m->v.trade();
-    return BDSP_OK;
-}
-
 // convolve_signal with a rows x rows matrix of impulse responses (convolve_mat, time_freq/mod.rs:365-453):
 //   out_row[n] = sum_r  row[r] (*) h[n][r]          (MIMO filtering; h row-major [n][r])
 template <typename T>
@@ -2561,13 +2551,6 @@ int mat_interpolatef_delays(DevMat<T>* m, int fid, T rolloff, T factor, const T*
     m->v.trade();
     m->v.valid_len = m->rows * new_len;
     return BDSP_OK;
-}
-
-template <typename T>
-int mat_multiply_frequency_response(DevMat<T>* m, int fid, T rolloff, T ratio)
-{
-    if (!m->v.freq) { m->v.poison(); return BDSP_OK; }
-    return ew_freq_response_rows<T>(m->v.data, m->rows, m->row_len(), m->v.complex_, fid, rolloff, ratio, false, lib_stream());
 }
 
 // diff / diff_with_start of every row (mat_scan.hip): each row as op_diff on it.  diff shortens every row by one point;
@@ -2914,22 +2897,6 @@ int mat_interpolate(DevMat<T>* m, int fid, T rolloff, size_t dest_points, T dela
     return BDSP_OK;
 }
 
-template <typename T>
-int mat_decimatei(DevMat<T>* m, unsigned factor, unsigned delay)
-{
-    if (factor == 0) return BDSP_ERR_ARG_LENGTH;
-    const size_t rows = m->rows, elem = m->v.complex_ ? 2 : 1, points = m->row_points();
-    if (rows == 0) return BDSP_OK;
-    const size_t outp = delay < points ? (points - delay + factor - 1) / factor : 0;
-    if (outp) {
-        BDSP_TRY(m->v.reserve(rows * outp * elem));
-        BDSP_TRY(rs_decimate_rows<T>(m->v.data, m->v.buf, rows, points, outp, elem, factor, delay, lib_stream()));
-        m->v.trade();
-    }
-    m->v.valid_len = rows * outp * elem;
-    return BDSP_OK;
-}
-
 // Symmetric real-signal transforms of the rows (matrix/src/time_freq.rs:83-107, 144-168, 173-177 forward the traits row
 // by row): every row behaves as op_sfft / op_sifft / op_mirror would on it.  Forward: the batched real-input transform,
 // then one crop of every row to its first p = N/2 + 1 bins.  Inverse: one launch that scales, rotates, tests the first
@@ -3037,15 +3004,6 @@ int mat_smaller(DevMat<T>* m, const DevMat<T>* o, int op)
 }
 
 // every row wraps around the same vector: its length must divide the ROW length, not the allocation's
-template <typename T>
-int mat_smaller_vector(DevMat<T>* m, const DevVec<T>* o, int op)
-{
-    const size_t rl = m->row_len(), yl = o->valid_len, e = m->v.complex_ ? 2 : 1;
-    if (yl == 0 || rl % yl != 0) return BDSP_ERR_ARG_LENGTH;
-    if (!meta_agrees(&m->v, o)) return BDSP_ERR_META_DATA;
-    return mw_smaller<T>(m->v.data, o->data, m->rows, rl / e, yl / e, 0, m->v.complex_, op, lib_stream());
-}
-
 // get_real / get_imag / get_magnitude / get_magnitude_squared / get_phase (kind as op_get_complex_to_real): `dst`
 // becomes m->rows rows of `points` reals and keeps its delta and domain; a real source or a complex destination leaves
 // it with m->rows empty rows.  The source is not consumed.
@@ -3633,7 +3591,7 @@ BDSP_STATS(64, double, VecBuf64)
     int32_t bdsp_hip_mat_fft_shift##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_swap<T>(&a->v, true, a->rows)); } \
     int32_t bdsp_hip_mat_ifft_shift##SFX(MB* m) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_swap<T>(&a->v, false, a->rows)); } \
     int32_t bdsp_hip_mat_zero_pad##SFX(MB* m, size_t points, int32_t option) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_zero_pad<T>(a, points, option)); } \
-    int32_t bdsp_hip_mat_convolve_signal##SFX(MB* m, const VB* impulse_response) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_convolve_signal<T>(a, H<T>(impulse_response))); } \
+    int32_t bdsp_hip_mat_convolve_signal##SFX(MB* m, const VB* impulse_response) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_convolve_signal<T>(&a->v, H<T>(impulse_response), a->rows)); } \
     int32_t bdsp_hip_mat_convolve_signal_mat##SFX(MB* m, const VB* const* impulse_responses, size_t count)  \
     { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_convolve_mimo<T>(a, reinterpret_cast<const DevVec<T>* const*>(impulse_responses), count)); } \
     int32_t bdsp_hip_mat_interpolatef##SFX(MB* m, int32_t impulse_response, T rolloff, T interpolation_factor, T delay, size_t conv_len) \
@@ -3641,7 +3599,7 @@ BDSP_STATS(64, double, VecBuf64)
     int32_t bdsp_hip_mat_interpolatef_delays##SFX(MB* m, int32_t impulse_response, T rolloff, T interpolation_factor, const T* delays, size_t count, size_t conv_len) \
     { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_interpolatef_delays<T>(a, impulse_response == 0 ? 0 : 1, rolloff, interpolation_factor, delays, count, conv_len)); } \
     int32_t bdsp_hip_mat_multiply_frequency_response##SFX(MB* m, int32_t frequency_response, T rolloff, T ratio) \
-    { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_multiply_frequency_response<T>(a, frequency_response == 0 ? 0 : 1, rolloff, ratio)); }
+    { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_multiply_frequency_response<T>(&a->v, frequency_response == 0 ? 0 : 1, rolloff, ratio, a->rows)); }
 
 BDSP_MAT(32, float, MatBuf32, VecBuf32)
 BDSP_MAT(64, double, MatBuf64, VecBuf64)
@@ -3736,7 +3694,7 @@ BDSP_MAT_SCAN(64, double, MatBuf64)
     int32_t bdsp_hip_mat_interpft##SFX(MB* m, size_t dest_points)                                           \
     { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_interpolate<T>(a, -1, (T)0, dest_points, (T)0)); } \
     int32_t bdsp_hip_mat_decimatei##SFX(MB* m, uint32_t decimation_factor, uint32_t delay)                  \
-    { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_decimatei<T>(a, decimation_factor, delay)); }
+    { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_decimatei<T>(&a->v, decimation_factor, delay, a->rows)); }
 
 BDSP_MAT_RESAMPLE(32, float, MatBuf32)
 BDSP_MAT_RESAMPLE(64, double, MatBuf64)
@@ -3819,10 +3777,10 @@ BDSP_MAT_INTERP(64, double, MatBuf64)
     int32_t bdsp_hip_mat_sub_smaller##SFX(MB* m, const MB* o) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_smaller<T>(a, MC##SFX(o), 1)); } \
     int32_t bdsp_hip_mat_mul_smaller##SFX(MB* m, const MB* o) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_smaller<T>(a, MC##SFX(o), 2)); } \
     int32_t bdsp_hip_mat_div_smaller##SFX(MB* m, const MB* o) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_smaller<T>(a, MC##SFX(o), 3)); } \
-    int32_t bdsp_hip_mat_add_smaller_vector##SFX(MB* m, const VB* o) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_smaller_vector<T>(a, H<T>(o), 0)); } \
-    int32_t bdsp_hip_mat_sub_smaller_vector##SFX(MB* m, const VB* o) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_smaller_vector<T>(a, H<T>(o), 1)); } \
-    int32_t bdsp_hip_mat_mul_smaller_vector##SFX(MB* m, const VB* o) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_smaller_vector<T>(a, H<T>(o), 2)); } \
-    int32_t bdsp_hip_mat_div_smaller_vector##SFX(MB* m, const VB* o) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, mat_smaller_vector<T>(a, H<T>(o), 3)); } \
+    int32_t bdsp_hip_mat_add_smaller_vector##SFX(MB* m, const VB* o) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_binary_smaller<T>(&a->v, H<T>(o), 0, a->rows)); } \
+    int32_t bdsp_hip_mat_sub_smaller_vector##SFX(MB* m, const VB* o) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_binary_smaller<T>(&a->v, H<T>(o), 1, a->rows)); } \
+    int32_t bdsp_hip_mat_mul_smaller_vector##SFX(MB* m, const VB* o) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_binary_smaller<T>(&a->v, H<T>(o), 2, a->rows)); } \
+    int32_t bdsp_hip_mat_div_smaller_vector##SFX(MB* m, const VB* o) { DevMat<T>* a = M##SFX(m); return mat_code<T>(a, op_binary_smaller<T>(&a->v, H<T>(o), 3, a->rows)); } \
     int32_t bdsp_hip_mat_get_real##SFX(const MB* m, MB* destination) { return mat_get_part<T>(MC##SFX(m), M##SFX(destination), 2); } \
     int32_t bdsp_hip_mat_get_imag##SFX(const MB* m, MB* destination) { return mat_get_part<T>(MC##SFX(m), M##SFX(destination), 3); } \
     int32_t bdsp_hip_mat_get_magnitude##SFX(const MB* m, MB* destination) { return mat_get_part<T>(MC##SFX(m), M##SFX(destination), 0); } \

@@ -101,15 +101,15 @@ template <typename T, bool ROWS = false> struct OpWindow {
     }
 };
 // multiply_function_priv, symmetric functions (time_freq/mod.rs:655-721): element i takes the value
-// of the function on the negative half of the axis, j = -|i - center|.  ROWS as in OpWindow.
-template <typename T, bool ROWS = false> struct OpFreqResp {
+// of the function on the negative half of the axis, j = -|i - center|.  Rows as OpWindow<T, true> (a vector is one row).
+template <typename T> struct OpFreqResp {
     struct Params { int id; T rolloff; T ratio; size_t points; int is_complex; int shifted; size_t row_len; };
     static __device__ __forceinline__ void apply(T* e, int n, size_t i0, Params p)
     {
         const size_t offset = p.points % 2;
         const T maxv = (T)(p.points - offset) / (T)2;
         const int step = p.is_complex ? 2 : 1;
-        size_t q = ROWS ? i0 % p.row_len : i0;
+        size_t q = i0 % p.row_len;
         for (int i = 0; i + step - 1 < n; i += step) {
             T j = -maxv + (T)(q / step);
             if (j > (T)0) j = -j;
@@ -120,7 +120,7 @@ template <typename T, bool ROWS = false> struct OpFreqResp {
                 e[i + 1] = re * (T)0 + im * arg;
             } else e[i] = e[i] * arg;
             q += step;
-            if (ROWS && q >= p.row_len) q = 0;
+            if (q >= p.row_len) q = 0;
         }
     }
 };
@@ -180,16 +180,11 @@ template <typename T> int ew_window_rows(T* x, size_t rows, size_t row_len, bool
 }
 template <typename T> int ew_fill(T* x, size_t len, T value, hipStream_t s)
 { return launch_map<T, OpFill<T>>(x, len, {value}, s); }
-template <typename T> int ew_freq_response(T* x, size_t len, bool is_complex, int fid, T rolloff, T ratio, bool shifted, hipStream_t s)
-{
-    size_t points = is_complex ? len / 2 : len;
-    return launch_map<T, OpFreqResp<T>>(x, len, {fid, rolloff, ratio, points, (int)is_complex, (int)shifted, len}, s);
-}
 template <typename T> int ew_freq_response_rows(T* x, size_t rows, size_t row_len, bool is_complex, int fid, T rolloff, T ratio, bool shifted, hipStream_t s)
 {
     if (rows == 0 || row_len == 0) return BDSP_OK;
     size_t points = is_complex ? row_len / 2 : row_len;
-    return launch_map<T, OpFreqResp<T, true>>(x, rows * row_len, {fid, rolloff, ratio, points, (int)is_complex, (int)shifted, row_len}, s);
+    return launch_map<T, OpFreqResp<T>>(x, rows * row_len, {fid, rolloff, ratio, points, (int)is_complex, (int)shifted, row_len}, s);
 }
 template <typename T> int ew_linear_phase(T* x, size_t len, T delay, hipStream_t s)
 {
@@ -428,7 +423,6 @@ template <typename T> int ew_complex_to_real(const T* x, T* out, size_t len, int
     template int ew_window<T>(T*, size_t, bool, int, T, bool, hipStream_t);                        \
     template int ew_window_rows<T>(T*, size_t, size_t, bool, int, T, bool, hipStream_t);           \
     template int ew_fill<T>(T*, size_t, T, hipStream_t);                                            \
-    template int ew_freq_response<T>(T*, size_t, bool, int, T, T, bool, hipStream_t);              \
     template int ew_freq_response_rows<T>(T*, size_t, size_t, bool, int, T, T, bool, hipStream_t); \
     template int ew_linear_phase<T>(T*, size_t, T, hipStream_t);                                    \
     template int ew_spectrum_resample<T>(const T*, T*, size_t, size_t, int, int, T, T, double, hipStream_t);

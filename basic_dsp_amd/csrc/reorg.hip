@@ -1,7 +1,8 @@
-// reorg.hip -- pure index moves (bit-exact): zero_interleave, decimatei and the circular extension of the long-filter
+// reorg.hip -- pure index moves (bit-exact): zero_interleave and the circular extension of the long-filter
 // convolution.  All out-of-place (the handle trades buffers afterwards, like the reference's Buffer::trade,
 // vector/src/vector_types/support_std.rs:78-82).  The moves that know rows -- swap_halves / fft_shift / ifft_shift,
-// zero_pad, reverse, mirror -- serve vectors and matrices alike from mat_frame.hip, mat_ew.hip and mat_sym.hip.
+// zero_pad, reverse, mirror, decimatei -- serve vectors and matrices alike from mat_frame.hip, mat_ew.hip, mat_sym.hip and
+// mat_resample.hip.
 //   zero_interleave   vector/src/vector_types/general/data_reorganization.rs:237-479
 #include "bdsp_internal.h"
 
@@ -57,15 +58,6 @@ __global__ __launch_bounds__(256) void k_zero_interleave2(const P* __restrict__ 
     }
 }
 
-// decimatei (interpolation.rs:607-633): out[j] = in[delay + j*factor]
-template <typename P, typename IDX>
-__global__ __launch_bounds__(256) void k_decimate(const P* __restrict__ in, P* __restrict__ out, IDX out_points,
-                                                   IDX factor, IDX delay)
-{
-    for (IDX j = (IDX)blockIdx.x * blockDim.x + threadIdx.x; j < out_points; j += (IDX)gridDim.x * blockDim.x)
-        out[j] = in[delay + j * factor];
-}
-
 // out[i] = in[(start + i) mod points], i < total (total may exceed points): the circular extension the
 // long-filter overlap-save path transforms its overlapping windows from
 template <typename P, typename IDX>
@@ -91,15 +83,6 @@ __global__ __launch_bounds__(256) void k_wrap_copy(const P* __restrict__ in, P* 
         }                                                                                                      \
         BDSP_LAUNCH_CHECK();                                                                                   \
     } while (0)
-
-template <typename T> int rg_decimate(const T* in, T* out, size_t out_points, size_t elem, size_t factor, size_t delay, hipStream_t s)
-{
-    if (out_points == 0) return BDSP_OK;
-#define BDSP_RG_ARGS(P, I) reinterpret_cast<const P*>(in), reinterpret_cast<P*>(out), (I)out_points, (I)factor, (I)delay
-    BDSP_RG_LAUNCH(k_decimate, (delay + out_points * factor) > out_points ? delay + out_points * factor : out_points);
-#undef BDSP_RG_ARGS
-    return BDSP_OK;
-}
 
 template <typename T> int rg_wrap_copy(const T* in, T* out, size_t points, size_t elem, size_t total, long long start, hipStream_t s)
 {
@@ -128,8 +111,7 @@ template <typename T> int rg_zero_interleave(const T* in, T* out, size_t len, si
 }
 #define BDSP_INST(T)                                                                               \
     template int rg_wrap_copy<T>(const T*, T*, size_t, size_t, size_t, long long, hipStream_t);    \
-    template int rg_zero_interleave<T>(const T*, T*, size_t, size_t, size_t, hipStream_t);         \
-    template int rg_decimate<T>(const T*, T*, size_t, size_t, size_t, size_t, hipStream_t);
+    template int rg_zero_interleave<T>(const T*, T*, size_t, size_t, size_t, hipStream_t);
 BDSP_INST(float)
 BDSP_INST(double)
 #undef BDSP_INST

@@ -4,7 +4,12 @@ end behind a pulse compressor.
 
 Tolerances are the ones the project holds the vector path to (test_gpu_parity.py,
 test_interpolatei_interpolate_decimatei): interpolatei rel-L2 < 5e-6 (f32) / 1e-11 (f64), interpolate / interpft
-< 2e-5 / 1e-10, decimatei bit-equal."""
+< 2e-5 / 1e-10, decimatei bit-equal.
+
+Since the second batch of DESIGN.md 4.4 DspVec.decimatei launches k_rs_decimate_rows with one row through the same host
+function, so decimatei "against the vector path" no longer spans two implementations (the vector's own reference:
+tests/test_gpu_vec_one_row.py); interpolatei, interpolate and interpft against the vector path still do: the vector keeps
+k_spectrum_resample and ew_linear_phase, and never takes the fused kernel."""
 import numpy as np
 import pytest
 

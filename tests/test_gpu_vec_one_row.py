@@ -23,6 +23,20 @@ References and bounds:
     1.6e-5 at 3000 points, 2.6e-3 at 524289, 5.3e-3 at 1048579 in f32; 2.6e-14, 4.4e-12, 8.7e-12 in f64 -- linear in
     the length), so above 3000 points that bound grows by points / 3000, which keeps test_gpu_parity's margin over the
     reference's own error.
+
+The second batch: multiply_frequency_response (the packet map with OpFreqResp, which carries the position in the row) and
+decimatei (k_rs_decimate_rows) launch with one row as well, and convolve_signal, *_smaller, multiply_frequency_response and
+decimatei have ONE host function for vectors and matrices.  Windows, the FFT-domain resampling family, interpolate_lin /
+interpolate_hermite, convolve(function) and the padding of correlate keep their vector kernels (one long row measured
+slower through the row-aware kernel), so the matrix tests still compare two implementations there.
+  * multiply_frequency_response: 1 .. 5 scalars (the tail below one 16-byte packet), lengths that make 1023, 1024 and 1025
+    packets (k_map_inplace's chunk of 1024 packets) and one grid stride + 1; against oracle_lib with
+    test_gpu_mat_basic's bounds: 1e-12 absolute in f64, 4 ulp of max |reference| in f32;
+  * decimatei: 1, 2, 3, 127, 128, 129, 255, 256, 257 output points (rs_row_geometry narrows the workgroup below 256 columns
+    and leaves blockDim.y > 1 with a single row), and one f32 real case of more than 65 535 x 256 outputs (the x dimension
+    of the grid is not clamped); bit-equal to oracle_lib;
+  * the merged host functions: poisoned input, wrong number space or domain, empty vector, with the codes of
+    tests/test_gpu_vec_sequences.py's tables.
 """
 import numpy as np
 import pytest
@@ -199,3 +213,130 @@ def test_smaller_bit_equal_to_the_oracle(shapes, cplx, dtype):
             v = DspVec(x, is_complex=cplx)
             assert v.add_smaller(DspVec(np.ones((p - 1) * e, dtype), is_complex=cplx)) == 7
             assert same_bits(v.data(), np.array(x)), p
+
+
+# ---------------------------------------------------------------------------------------------- second batch
+EW_CHUNK = 1024   # ew_map.h: packets of 16 bytes per workgroup chunk
+MFR_RATIO, MFR_ROLLOFF = 1.7, 0.35   # tests/test_gpu_mat_basic.py
+
+
+def _packet_points(cplx, dtype, stride):
+    """points whose scalars are 1 .. 5 (complex: 2 and 4), 1023 / 1024 / 1025 packets of 16 bytes, and one grid stride + 1"""
+    e, per_packet = (2 if cplx else 1), 16 // np.dtype(dtype).itemsize
+    small = [n // e for n in range(1, 6) if n % e == 0]
+    return small + [k * per_packet // e for k in (EW_CHUNK - 1, EW_CHUNK, EW_CHUNK + 1)] + [stride + 1]
+
+
+def _close_where_finite(got, ref, dtype, what):
+    """test_gpu_mat_basic's bounds for multiply_frequency_response; one point has no axis (0 / 0): NaN where the oracle's is"""
+    assert got.dtype == ref.dtype and got.shape == ref.shape, what
+    nan = np.isnan(ref)
+    assert np.array_equal(np.isnan(got), nan), what
+    if nan.all():
+        return
+    g, r = got[~nan].astype(np.float64), ref[~nan].astype(np.float64)
+    if dtype == np.float64:
+        assert np.max(np.abs(g - r)) <= 1e-12, (what, np.max(np.abs(g - r)))
+    else:
+        top = np.max(np.abs(r))
+        ulp = float(np.spacing(np.float32(top if top > 0 else 1.0)))
+        assert np.max(np.abs(g - r)) <= 4.0 * ulp, (what, np.max(np.abs(g - r)) / ulp)
+
+
+@pytest.mark.parametrize("cplx,dtype", CASES, ids=IDS)
+def test_multiply_frequency_response_against_the_oracle(shapes, cplx, dtype):
+    e = 2 if cplx else 1
+    stride = shapes[-2] - 1
+    for p in _packet_points(cplx, dtype, stride):
+        x = unaligned(orc.fill_uniform(p * e, 6000 + p % 1000, -1, 1, dtype))
+        for fid in (V.CONV_SINC, V.CONV_RAISED_COSINE):
+            v = DspVec(x, is_complex=cplx, domain=V.FREQ, delta=0.25)
+            assert v.multiply_frequency_response(fid, MFR_RATIO, MFR_ROLLOFF) == 0, (p, fid)
+            assert len(v) == p * e and v.is_complex() == cplx and v.domain() == V.FREQ and v.delta() == 0.25
+            with np.errstate(all="ignore"):
+                ref = orc.multiply_frequency_response(np.array(x), cplx, fid, MFR_ROLLOFF, MFR_RATIO, False)
+            _close_where_finite(v.data(), ref, dtype, (p, fid))
+
+
+DECIMATE_OUT = (1, 2, 3, 127, 128, 129, 255, 256, 257)
+
+
+@pytest.mark.parametrize("cplx,dtype", CASES, ids=IDS)
+def test_decimatei_bit_equal_to_the_oracle(cplx, dtype):
+    bd.require_gpu()
+    e = 2 if cplx else 1
+    for out in DECIMATE_OUT:
+        for factor, delay in ((3, 2), (2, 0), (1, 1)):
+            for p in (delay + (out - 1) * factor + 1, delay + out * factor):   # the shortest and the longest vector with `out` outputs
+                x = signal(p, cplx, dtype, seed=2)
+                v = DspVec(x, is_complex=cplx)
+                assert v.decimatei(factor, delay) == 0, (p, factor, delay)
+                ref = orc.decimatei(np.array(x), cplx, factor, delay)
+                assert len(v) == ref.size == out * e, (p, factor, delay)
+                assert same_bits(v.data(), ref), (p, factor, delay)
+    # a delay at or past the end leaves an empty vector
+    v = DspVec(signal(5, cplx, dtype, seed=2), is_complex=cplx)
+    assert v.decimatei(2, 5) == 0 and len(v) == 0 and not v.is_erroneous()
+
+
+def test_decimatei_with_more_outputs_than_65535_workgroups_of_256():
+    bd.require_gpu()
+    out = 65535 * 256 + 257
+    x = np.resize(signal(1 << 20, False, np.float32, seed=3), 2 * out + 1)
+    v = DspVec(x)
+    assert v.decimatei(2, 1) == 0 and len(v) == out
+    assert same_bits(v.data(), x[1::2])
+    assert same_bits(x[1::2][:4099], orc.decimatei(np.array(x[:8199]), False, 2, 1))   # (the slice is what the oracle computes)
+
+
+@pytest.mark.parametrize("cplx,dtype", CASES, ids=IDS)
+def test_codes_of_the_merged_host_functions(cplx, dtype):
+    """op_convolve_signal, op_binary_smaller, op_multiply_frequency_response and op_decimatei serve vectors and matrices: a
+    poisoned vector, the wrong number space or domain and an empty vector, with the codes of tests/test_gpu_vec_sequences.py
+    (_arg_errors, _poisoners, the unrelated calls on a poisoned vector) and tests/test_gpu_mat_basic.py (convolve_signal on
+    a poisoned or empty matrix)"""
+    bd.require_gpu()
+    e = 2 if cplx else 1
+    x13 = signal(13, cplx, dtype, seed=4)
+    x = x13[:12 * e]
+
+    def mk(n=12, c=cplx, domain=V.TIME):
+        return DspVec(np.array(x13[:n * e] if c == cplx else np.ones(n * (2 if c else 1), dtype)), is_complex=c, domain=domain)
+
+    def poisoned():
+        v = mk()
+        assert (v.to_complex() if cplx else v.conj()) == -1 and v.is_erroneous()
+        return v
+
+    def untouched(v, domain=V.TIME):
+        return len(v) == 12 * e and v.domain() == domain and same_bits(v.data(), np.array(x))
+
+    # convolve_signal: 2 number space, 2 domain, 5 both in the frequency domain, 7 filter longer than the vector
+    for bad, code in ((mk(6, not cplx), 2), (mk(6, cplx, V.FREQ), 2), (mk(13), 7)):
+        v = mk()
+        assert v.convolve_signal(bad) == code and untouched(v), code
+    v = mk(domain=V.FREQ)
+    assert v.convolve_signal(mk(6, cplx, V.FREQ)) == 5 and untouched(v, V.FREQ)
+    v = mk()
+    assert v.convolve_signal(mk(0)) == 0 and untouched(v)            # an empty filter leaves the vector alone
+    assert mk(0).convolve_signal(mk(0)) == 0 and mk(0).convolve_signal(mk(3)) == 7
+    assert poisoned().convolve_signal(mk(0)) == -1 and poisoned().convolve_signal(mk(3)) == 7   # an argument error comes first
+    # *_smaller: 7 empty operand or a length that does not divide, 2 domain
+    for name in ("add_smaller", "sub_smaller", "mul_smaller", "div_smaller"):
+        for bad, code in ((mk(0), 7), (mk(5), 7), (mk(6, cplx, V.FREQ), 2)):
+            v = mk()
+            assert getattr(v, name)(bad) == code and untouched(v), (name, code)
+        assert getattr(mk(0), name)(mk(3)) == 0 and getattr(poisoned(), name)(mk(3)) == -1, name
+    # multiply_frequency_response: a time-domain vector is poisoned; empty and poisoned vectors
+    v = mk()
+    assert v.multiply_frequency_response(V.CONV_SINC, 0.5) == -1 and v.is_erroneous()
+    v = mk(0, cplx, V.FREQ)
+    assert v.multiply_frequency_response(V.CONV_SINC, 0.5) == 0 and len(v) == 0 and not v.is_erroneous()
+    assert poisoned().multiply_frequency_response(V.CONV_RAISED_COSINE, 0.5, 0.35) == -1
+    # decimatei: 7 by 0; empty and poisoned vectors
+    v = mk()
+    assert v.decimatei(0, 0) == 7 and untouched(v)
+    v = mk(0)
+    assert v.decimatei(2, 0) == 0 and len(v) == 0 and not v.is_erroneous()
+    v = poisoned()
+    assert v.decimatei(2, 0) == -1 and v.is_erroneous() and v.decimatei(0, 0) == 7

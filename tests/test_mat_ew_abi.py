@@ -25,8 +25,7 @@ PARTS = ("get_real", "get_imag", "get_magnitude", "get_magnitude_squared", "get_
 ENTRIES = MATH0 + MATH1 + ROW_AWARE + PARTS
 METHODS = MATH0 + MATH1 + ("reverse", "multiply_complex_exponential") + SMALLER + PARTS
 ROW_HOST_FUNCTIONS = ("op_reverse",)  # one body for vectors and matrices (rows = 1 by default)
-HOST_FUNCTIONS = ("mat_mul_cexp", "mat_smaller", "mat_smaller_vector", "mat_get_part", "mat_get_pair",
-                  "mat_set_pair")
+HOST_FUNCTIONS = ("mat_mul_cexp", "mat_smaller", "mat_get_part", "mat_get_pair", "mat_set_pair")
 
 
 def expected_names():
@@ -95,8 +94,17 @@ def test_no_row_loop_and_no_synchronise_in_the_new_host_functions():
     assert "mw_reverse<T>(" in shared
     assert not [b for b in banned if b in shared]
     assert not re.search(r"\b(for|while)\s*\(", shared)
+    # *_smaller_vector: op_binary_smaller, the vector's host function, with the matrix's rows (mat_smaller_vector is gone)
+    assert "int mat_smaller_vector(" not in src
+    start = src.index("int op_binary_smaller(")
+    smaller = src[start:src.index("\ntemplate <", start)]
+    assert "size_t rows = 1)" in smaller.split("\n")[0] and "mw_smaller<T>(" in smaller
+    assert not [b for b in banned if b in smaller]
+    assert not re.search(r"\b(for|while)\s*\(", smaller)
     entries = src[src.index("#define BDSP_MAT_EW_M0("):src.index("#undef BDSP_MAT_EW\n")]
     assert "op_reverse<T>(&a->v, a->rows)" in entries
+    for op in range(4):
+        assert "op_binary_smaller<T>(&a->v, H<T>(o), %d, a->rows)" % op in entries
     assert entries.count("op_math<T>(&a->v") == 3  # the two macros of the family and root
     assert not [b for b in banned if b in entries] and not re.search(r"\b(for|while)\s*\(", entries)
     with open(os.path.join(CSRC, "mat_ew.hip")) as f:

@@ -43,15 +43,23 @@ def test_python_binds_the_methods():
 
 
 def test_no_row_loop_in_the_new_host_functions():
-    """mat_interpolatei / mat_interpolate / mat_decimatei and their helpers use neither mat_each_row nor mat_resize_rows"""
+    """mat_interpolatei / mat_interpolate and their helpers, and op_decimatei (one body for vectors and matrices, rows = 1
+    by default; mat_decimatei is gone), use neither mat_each_row nor mat_resize_rows"""
     with open(os.path.join(CSRC, "capi.cpp")) as f:
         src = f.read()
     start = src.index("int mat_resample_general(")
     end = src.index("} // namespace", start)
     body = src[start:end]
-    for n in ("mat_resample_fused", "mat_interpolatei", "mat_interpolate", "mat_decimatei"):
+    for n in ("mat_resample_fused", "mat_interpolatei", "mat_interpolate"):
         assert "int %s(" % n in body, n
+    assert "int mat_decimatei(" not in src
+    start = src.index("int op_decimatei(")
+    shared = src[start:src.index("\ntemplate <", start)]
+    assert "size_t rows = 1)" in shared.split("\n")[0] and "rs_decimate_rows<T>(" in shared
+    assert "op_decimatei<T>(&a->v, decimation_factor, delay, a->rows)" in src   # the matrix entry points
+    body += shared
     assert "mat_each_row" not in body and "mat_resize_rows" not in body
+    assert not re.search(r"\b(for|while)\s*\(", shared)
 
 
 def test_mat_resample_builds_without_warnings(tmp_path):
